@@ -4,6 +4,14 @@ composite [-> exchange -> gather / reduce]) and the frame's achieved HBM GB/s,
 on BASELINE.json's workloads, inputs resident in HBM before the timed region.
 
   python bench.py [--gpus N --steps K --warmup W --config 1080p|4k|50m|1m]
+                   [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it builds the
+scene, runs W untimed frames, times K frames, writes the last timed frame under
+--dump-outputs when that is given, and prints the result line.  Everything
+else this file measures (the settled and orbit probes, kernel and stage
+timing, the roofline with its rocprofv3 PMC passes, the CPU baselines) takes
+frames or processes of its own and runs only with --full.
 
 Workloads (seeded synthetic scenes with 3DGS statistics; the garden .ply
 does not exist offline):
@@ -38,7 +46,7 @@ The north star's depth slabs + transmittance all_gather + RGBA reduce
 (--scheme slabs / both) do NOT meet its 1e-4 tolerance (pixels at the 0.99
 break) and are not part of the default run.
 
-At N=1 the line also carries
+With --full the line at N=1 also carries
   roofline      the dominant kernel's algorithmic bytes / its standalone
                 duration (HIP events in its own dispatch packet, extra
                 unpipelined frames), and `kernels`: preprocess and composite
@@ -55,7 +63,15 @@ At N=1 the line also carries
   cpu_baseline  the CPU oracle (oracle/gs_oracle.c, OpenMP) on the same scene
                 and camera on all host threads, and on 1 thread over a
                 bounded subset (cpu_baseline_1core)
-Prints one JSON line on rank 0.
+(with --full the multi-GPU line carries `settled` too).  Prints one JSON line
+on rank 0.
+
+--dump-outputs DIR writes what the timed path returned from its last timed
+frame: DIR/frame.npy, float32 [H, W, 4] premultiplied RGBA (the headline
+scheme's frame at N>1, on rank 0).  A frame above DUMP_LIMIT bytes is written
+as a fixed seeded sample of its pixels, [k, 4], beside DIR/frame_pixels.npy
+(float64 [k], the flat pixel indices y*W + x).  Scene, camera and sample depend
+on the arguments alone, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -76,6 +92,7 @@ sys.path.insert(0, str(ROOT))
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec (MI355X_MICROARCH.md)
 SIMDS = 1024                 # 256 CUs x 4 SIMD-32
 CLOCK_HZ = 2.4e9             # peak engine clock
+DUMP_LIMIT = 48 << 20        # --dump-outputs: bytes of frame written whole; above it a seeded sample, this size with its indices
 VALU_ISSUE_CYC = 2           # cycles per wave64 VALU instruction per SIMD, waves interleaved (MI355X_MICROARCH.md:54)
 
 CONFIGS = {
@@ -95,6 +112,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the settled and orbit probes, kernel and "
+                         "stage timing, the roofline's PMC passes and the CPU baselines (--settled-probe, "
+                         "--orbit-probe, --no-stage-timing, --pmc, --cpu-baseline and --cpu-seconds apply to these "
+                         "and are ignored without --full)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed frames, write the last timed frame as DIR/frame.npy (float32 RGBA; above "
+                         "DUMP_LIMIT bytes a fixed seeded sample of its pixels, indices in DIR/frame_pixels.npy)")
     ap.add_argument("--settle", type=int, default=0,
                     help="untimed frames before the warmup (0 = the warmup alone, as the driver runs it)")
     ap.add_argument("--settled-probe", type=int, default=60,
@@ -134,6 +159,9 @@ def parse():
     ap.add_argument("--comm-timeout", type=float, default=120.0,
                     help="N>1: seconds before a rendezvous or collective that a peer never joins fails")
     a = ap.parse_args()
+    if not a.full:  # a plain run: the timed frames alone
+        a.settled_probe = a.orbit_probe = a.cpu_baseline = a.pmc = 0
+        a.no_stage_timing = True
     c = CONFIGS[a.config]
     a.splats = a.splats or c["splats"]
     a.width = a.width or c["width"]
@@ -143,6 +171,26 @@ def parse():
     a.label = c["label"] if (a.splats, a.width, a.height, a.sh) == (c["splats"], c["width"], c["height"], c["sh"]) \
         else f"{a.splats} splats @{a.width}x{a.height}, SH{a.sh}"
     return a
+
+
+def snapshot(frame):
+    """A host copy of a frame the timed path returned (a device tensor)."""
+    return frame.detach().to("cpu").numpy().astype(np.float32, copy=True)
+
+
+def dump_outputs(path, frame) -> None:
+    """--dump-outputs: DIR/frame.npy, whole up to DUMP_LIMIT bytes, else a
+    fixed seeded sample of the pixels and their flat indices."""
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    px = np.ascontiguousarray(frame, np.float32)
+    if px.nbytes > DUMP_LIMIT:
+        flat = px.reshape(-1, px.shape[-1])
+        k = DUMP_LIMIT // (flat.shape[1] * 4 + 8)  # (sample and indices together within the limit)
+        idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=k, replace=False))
+        np.save(d / "frame_pixels.npy", idx.astype(np.float64))
+        px = flat[idx]
+    np.save(d / "frame.npy", px)
 
 
 def spawn_ranks(args) -> int:
@@ -223,7 +271,7 @@ def pmc_passes(args):
     exe = shutil.which("rocprofv3")
     if not exe:
         return None, "rocprofv3 not found"
-    bench = [sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--settle", "0", "--cpu-baseline", "0",
+    bench = [sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--settle", "0", "--cpu-baseline", "0",
              "--pmc", "0", "--orbit-probe", "0", "--no-stage-timing", "--frames-in-flight", "1", "--splats", str(args.splats),
              "--width", str(args.width), "--height", str(args.height), "--sh", str(args.sh), "--mode", args.mode,
              "--seed", str(args.seed), "--profile", args.profile]
@@ -331,10 +379,12 @@ def group_main(args):
         else:
             step = (lambda g_=g: g_.render(view, proj, W, H, out=out))
         schemes[sch] = {"ms": timed(step, args.steps, args.warmup, drain), "step": step, "drain": drain,
-                        "transport": g.transport}
+                        "transport": g.transport, "frame": snapshot(out) if args.dump_outputs else None}
         groups[sch] = g
     head, exact = headline(schemes, order)
     ms = schemes[head]["ms"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, schemes[head]["frame"])
     settled_line = None
     if args.settled_probe > 0:
         for _ in range(args.settled_probe):
@@ -427,6 +477,7 @@ def main():
                    frames_in_flight=args.frames_in_flight if world == 1 else 1)
 
     settled = {"frames": 0, "ms": 0.0}
+    last = {"frame": None}  # what the timed path returned last (--dump-outputs)
 
     def timed(step, steps, warmup, settle=None, drain=None):
         # --settle: untimed frames before the warmup (default none, the
@@ -449,9 +500,9 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            step()
+            last["frame"] = step()
         if drain is not None:  # (pipelined row frames: the last frame finishes inside the timed region)
-            drain()
+            last["frame"] = drain()
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -489,14 +540,16 @@ def main():
             frame = [0]
 
             def step():
-                r.render(views[frame[0] % len(views)], proj, W, H, out=out)
+                img = r.render(views[frame[0] % len(views)], proj, W, H, out=out)
                 frame[0] += 1
+                return img
         else:
             step = lambda: r.render(view, proj, W, H, out=out)
         rh = r
         drain = None
         ms = timed(step, args.steps, args.warmup)
         s_timed = r.last_stats()  # (the timed frames' lists, before the probes below move the camera)
+        dumped = snapshot(last["frame"]) if args.dump_outputs else None
         settled_line = settled_probe(step, args.steps)
         if args.camera == "fixed" and args.orbit_probe:
             # camera sensitivity: the default camera is the
@@ -558,12 +611,16 @@ def main():
             stp = (lambda s_=sr: s_.render(view, proj, W, H, gather=True))
             drn = getattr(sr, "flush", None) if getattr(sr, "pipeline", False) else None
             schemes[sch] = {"ms": timed(stp, args.steps, args.warmup, drain=drn), "handle": be.r, "step": stp,
-                            "drain": drn}
+                            "drain": drn,
+                            "frame": snapshot(last["frame"]) if args.dump_outputs and rank == 0 else None}
         head, exact = headline(schemes, order)
         ms, rh, step = schemes[head]["ms"], schemes[head]["handle"], schemes[head]["step"]
         drain = schemes[head]["drain"]
+        dumped = schemes[head]["frame"]
         settled_line = settled_probe(step, args.steps, drain=drain)
     value = N / (ms * 1e-3) / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dumped)
 
     s0 = s_timed if world == 1 else rh.last_stats()
     binning = {1: "depth-first", 2: "bin-first"}.get(int(s0.get("binning", 0)), "?")

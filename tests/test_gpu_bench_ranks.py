@@ -22,7 +22,7 @@ ROOT = Path(__file__).resolve().parents[1]
 
 def test_bench_two_rank_rehearsal(built):
     env = dict(os.environ, GS_BENCH_BACKEND="gloo", GS_BENCH_SAME_DEVICE="1")
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--launcher", "ranks", "--steps", "3", "--warmup",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "2", "--launcher", "ranks", "--steps", "3", "--warmup",
            "1", "--splats", "300000", "--cpu-baseline", "0", "--pmc", "0", "--settle", "2", "--settled-probe", "4"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=str(ROOT))
     assert p.returncode == 0, p.stderr[-2000:]
@@ -49,7 +49,7 @@ def test_bench_group_launcher_rehearsal(built):
     this one-GPU box: GS_RCCL_LIB, every rank on device 0)."""
     from gaussian_splat_amd.build import RCCL_STUB
     env = dict(os.environ, GS_BENCH_SAME_DEVICE="1", GS_RCCL_LIB=str(RCCL_STUB))
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "2",
            "--splats", "300000", "--cpu-baseline", "0", "--pmc", "0", "--settled-probe", "4"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=str(ROOT))
     assert p.returncode == 0, p.stderr[-2000:]

@@ -5,6 +5,7 @@
 #   bash tools/ab.sh [bench args]
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
+set -- --full "$@"  # (the stage times printed below come from the bench's extra frames)
 for so in ab/*.so; do
   name=$(basename "$so" .so)
   GSPLAT_LIB="$PWD/$so" timeout -k 10 300 python bench.py --cpu-baseline 0 --pmc 0 "$@" \

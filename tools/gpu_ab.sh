@@ -9,6 +9,7 @@ for v in ${PARITY}; do
   rc=$?; echo "$v parity rc=$rc $(tail -1 gpurun_out/pt_$v.log)"; [ $rc -eq 0 ] || exit $rc
 done
 VARIANTS="${VARIANTS:-$(ls ab/*.so | xargs -n1 basename | sed 's/\.so$//')}"
+BENCH_ARGS="--full ${BENCH_ARGS}"  # (the kernel and stage times printed below come from the bench's extra frames)
 for r in $(seq ${ROUNDS:-2}); do
   for v in $VARIANTS; do
     GSPLAT_LIB=$PWD/ab/$v.so timeout -k 10 300 python bench.py --cpu-baseline 0 --pmc 0 ${BENCH_ARGS} \

@@ -8,12 +8,13 @@ O=gpurun_out/art; mkdir -p $O
 step() { name=$1; shift; echo "== $name"; "$@"; rc=$?; echo "$name rc=$rc"; [ $rc -eq 0 ] || exit $rc; }
 for s in ${STEPS:-tests driver bench prof pmc configs heavy orbit ranks timeline scaling}; do case $s in
 driver) step driver bash -c "timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench_driver_command.err"
-       python -c "import json;d=json.load(open('$O/bench_driver_command.json'));print('driver', d['ms_per_step'], d['settled']['ms_per_step'], d['orbit']['ms_per_step'], d['roofline']['frac'], d['roofline']['kernels']['composite']['ms'])" ;;
+       python -c "import json;d=json.load(open('$O/bench_driver_command.json'));print('driver', d['ms_per_step'], d['value'])" ;;
 tests) step tests bash -c "timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread > $O/pytest_gpu.log 2>&1"
        tail -1 $O/pytest_gpu.log ;;
-bench) step bench bash -c "timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err"; cat $O/bench_default.json ;;
+bench) step bench bash -c "timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err"; cat $O/bench_default.json
+       python -c "import json;d=json.load(open('$O/bench_default.json'));print('bench', d['ms_per_step'], d['settled']['ms_per_step'], d['orbit']['ms_per_step'], d['roofline']['frac'], d['roofline']['kernels']['composite']['ms'])" ;;
 prof)  step prof bash -c "timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- \
-         python bench.py --frames-in-flight 1 --pmc 0 --cpu-baseline 0 > $O/bench_profiled.json 2> $O/bench_profiled.err"
+         python bench.py --full --frames-in-flight 1 --pmc 0 --cpu-baseline 0 > $O/bench_profiled.json 2> $O/bench_profiled.err"
        cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/bench_profiled_kernel_stats.csv; cat $O/bench_profiled.json ;;
 pmc)   B="python bench.py --steps 3 --warmup 1 --cpu-baseline 0 --pmc 0 --no-stage-timing --frames-in-flight 1"
        step sq1 timeout -s KILL 200 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU -d $O/pmc/sq1 -o run --output-format csv -- $B > $O/pmc_sq1.log 2>&1
@@ -32,7 +33,7 @@ prof50m) for c in 4k 50m; do
            python bench.py --config $c --steps 20 --frames-in-flight 1 --pmc 0 --cpu-baseline 0 --settled-probe 0 --orbit-probe 0 > $O/bench_${c}_profiled.json 2> $O/bench_${c}_profiled.err"
          cp $(find $O/prof_$c -name "*kernel_stats.csv" | head -1) $O/bench_${c}_profiled_kernel_stats.csv; done ;;
 configs) for c in 1m 4k 50m; do
-         step cfg_$c bash -c "timeout -k 10 600 python bench.py --config $c --steps 30 --cpu-baseline 0 > $O/bench_$c.json 2> $O/bench_$c.err"
+         step cfg_$c bash -c "timeout -k 10 600 python bench.py --full --config $c --steps 30 --cpu-baseline 0 > $O/bench_$c.json 2> $O/bench_$c.err"
          python -c "import json;d=json.load(open('$O/bench_$c.json'));print('$c', d['ms_per_step'], d['value'], d['config']['binning'], d['roofline']['kernels']['composite']['ms'])"; done ;;
 heavy) step heavy bash -c "timeout -k 10 600 python bench.py --profile heavy --steps 50 --cpu-baseline 0 > $O/bench_heavy.json 2> $O/bench_heavy.err"
        python -c "import json;d=json.load(open('$O/bench_heavy.json'));print('heavy', d['ms_per_step'], d['value'], d['config']['pairs'])" ;;

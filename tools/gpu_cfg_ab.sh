@@ -2,6 +2,7 @@
 # One config under several environments, interleaved: CFG (bench --config), ENVS ("name:ENV=VAL,ENV2=VAL ..."),
 # ROUNDS.  Prints frame ms, binning, pairs, pairs sorted and the stage times of each run.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out; export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS}"  # (the stage times printed below come from the bench's extra frames)
 for r in $(seq ${ROUNDS:-1}); do
 for c in $ENVS; do
   name=${c%%:*}; envs=${c#*:}; [ "$envs" = "$c" ] && envs=""

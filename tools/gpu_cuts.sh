@@ -7,6 +7,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
     > gpurun_out/pytest_gpu.log 2>&1; rc=$?
   tail -3 gpurun_out/pytest_gpu.log; echo "pytest rc=$rc"; [ $rc -eq 0 ] || { grep -E "^(FAILED|ERROR)|Error" gpurun_out/pytest_gpu.log | head -20; exit $rc; }
 fi
+BENCH_ARGS="--full ${BENCH_ARGS}"  # (the kernel and stage times printed below come from the bench's extra frames)
 for r in $(seq ${ROUNDS:-2}); do
   for cam in ${CAMS:-fixed orbit}; do
     for ds in 0 1; do

@@ -7,6 +7,7 @@ if [ -n "$PYTEST_K" ]; then
     > gpurun_out/pytest_gpu.log 2>&1; rc=$?
   tail -3 gpurun_out/pytest_gpu.log; echo "pytest rc=$rc"; [ $rc -eq 0 ] || { grep -E "^(FAILED|ERROR)" gpurun_out/pytest_gpu.log | head; exit $rc; }
 fi
+BENCH_ARGS="--full ${BENCH_ARGS}"  # (the kernel and stage times printed below come from the bench's extra frames)
 for r in $(seq ${ROUNDS:-2}); do
   for v in off $(ls ab/*.so | xargs -n1 basename | sed 's/\.so$//'); do
     if [ $v = off ]; then lib=$PWD/gaussian_splat_amd/libgsplat.so; ds=0; else lib=$PWD/ab/$v.so; ds=1; fi

@@ -1,6 +1,7 @@
 #!/bin/bash
 # A/B of (library variant, environment) pairs: CASES="name:lib:ENV=VAL,ENV2=VAL ..." (lib = ab/<lib>.so or "base")
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out; export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS}"  # (the kernel times and the roofline printed below come from the bench's extra frames)
 for r in $(seq ${ROUNDS:-2}); do
 for c in $CASES; do
   name=${c%%:*}; rest=${c#*:}; lib=${rest%%:*}; envs=${rest#*:}; [ "$envs" = "$rest" ] && envs=""

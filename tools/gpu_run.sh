@@ -5,6 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 STEPS="${STEPS:-tests bench prof}"
+BENCH_ARGS="${BENCH_ARGS:---full}"  # (the whole line by default: probes, kernel and stage times, roofline, CPU baseline)
 stop_if_bad() {  # rc 0 = pass, 1 = test failure (not a fault) -> continue
   rc=$1; what=$2
   echo "$what rc=$rc"

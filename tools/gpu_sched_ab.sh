@@ -4,6 +4,7 @@
 # times interleaved, optional PARITY (pytest -k expr, under PARITY_ENV or the defaults), then a
 # kernel-trace timeline of each config in TL (indices into CFGS).
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out; export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS}"  # (the kernel times printed below come from the bench's extra frames)
 read -ra C <<< "${CFGS:--}"
 envof() { [ "$1" = "-" ] && return; echo "$1" | tr ',' ' '; }
 if [ -n "$PARITY" ]; then
