@@ -109,7 +109,9 @@ def build_dropin_app(lib: Path = LIB) -> Path:
 
 
 RCCL_STUB_SRC = ROOT / "tests" / "cpp" / "rccl_stub.hip"
-RCCL_STUB = ROOT / "tests" / "cpp" / "librccl_stub.so"
+# (beside libgsplat.so, not in tests/: the test tree holds sources only, so a suite run from another
+# copy of tests/ against this build still finds it; loaded only through GS_RCCL_LIB)
+RCCL_STUB = PKG / "librccl_stub.so"
 
 
 def build_rccl_stub() -> Path:

@@ -168,7 +168,7 @@ def test_group_rccl_stub_bitexact(built):
 
     from gaussian_splat_amd.build import RCCL_STUB
     root = Path(__file__).resolve().parents[1]
-    assert RCCL_STUB.exists(), "build() makes tests/cpp/librccl_stub.so"
+    assert RCCL_STUB.exists(), "build() makes librccl_stub.so"
     env = dict(os.environ, GS_RCCL_LIB=str(RCCL_STUB))
     p = subprocess.run([sys.executable, "-c", _STUB_SCRIPT, str(root)], env=env, capture_output=True, text=True,
                        timeout=170)
@@ -378,7 +378,7 @@ def test_group_rccl_stub_pipelined_bitexact(built):
 
     from gaussian_splat_amd.build import RCCL_STUB
     root = Path(__file__).resolve().parents[1]
-    assert RCCL_STUB.exists(), "build() makes tests/cpp/librccl_stub.so"
+    assert RCCL_STUB.exists(), "build() makes librccl_stub.so"
     env = dict(os.environ, GS_RCCL_LIB=str(RCCL_STUB))
     p = subprocess.run([sys.executable, "-c", _STUB_PIPE_SCRIPT, str(root)], env=env, capture_output=True, text=True,
                        timeout=170)

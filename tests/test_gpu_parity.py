@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import check_slab_frame, orbit_views
+from pairs_ref import rect_bin_pairs as _rect_bin_pairs
 
 pytestmark = pytest.mark.gpu
 
@@ -33,33 +34,6 @@ def _compare(img, ref):
     linf = float(diff.max()) if diff.size else 0.0
     nbit = int(np.count_nonzero(img.view(np.uint32) != ref.view(np.uint32)))
     return linf, nbit
-
-
-def _rect_bin_pairs(rec, dk, nt, W):
-    """(bin, dkey, splat) for every 32x32 bin of every visible splat's rect
-    (the superset the bin lists are drawn from), and the set of (bin, splat)
-    pairs whose splat surely covers a pixel centre of the bin (float64,
-    threshold shrunk by 1e-4: must be present)."""
-    bx = (W + 31) // 32
-    qmax = 9.21034037197618 * (1.0 - 1e-4)
-    pairs, must = [], set()
-    for i in np.nonzero(nt)[0]:
-        lo, hi = int(rec["rect_lo"][i]), int(rec["rect_hi"][i])
-        x0, y0, x1, y1 = lo & 0xFFFF, lo >> 16, hi & 0xFFFF, hi >> 16
-        r = rec[i]
-        for by in range(y0 >> 5, (y1 >> 5) + 1):
-            for b in range(x0 >> 5, (x1 >> 5) + 1):
-                key = by * bx + b
-                pairs.append((key, int(dk[i]), int(i)))
-                px = np.arange(max(b * 32, x0), min(b * 32 + 31, x1) + 1) + 0.5
-                py = np.arange(max(by * 32, y0), min(by * 32 + 31, y1) + 1) + 0.5
-                dx = px[None, :] - float(r["cx"])
-                dy = float(r["cy"]) - py[:, None]
-                u = dy * float(r["ay"]) + dx * float(r["ax"])
-                v = dy * float(r["by"]) + dx * float(r["bx"])
-                if np.any((u * u + v * v <= qmax) & (np.maximum(np.abs(u), np.abs(v)) <= 3.0 * (1 - 1e-5))):
-                    must.add((key, int(i)))
-    return pairs, must
 
 
 @pytest.mark.parametrize("sh", [0, 1, 2, 3])

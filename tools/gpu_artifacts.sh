@@ -51,7 +51,7 @@ ranks) step ranks bash -c "GS_BENCH_BACKEND=gloo GS_BENCH_SAME_DEVICE=1 timeout 
        grep '^{' $O/rehearsal_2rank_gloo.log > $O/rehearsal_2rank_gloo.json; cat $O/rehearsal_2rank_gloo.json
        # the one-process launcher (bench.py's default outside torchrun) through the group's RCCL
        # branches, on device 0 with the test stub of the RCCL entry points
-       step group bash -c "GS_BENCH_SAME_DEVICE=1 GS_RCCL_LIB=$PWD/tests/cpp/librccl_stub.so timeout -k 10 600 python bench.py --gpus 2 --steps 10 --warmup 3 --cpu-baseline 0 --pmc 0 > $O/rehearsal_2rank_group_stub.json 2> $O/rehearsal_2rank_group_stub.err"
+       step group bash -c "GS_BENCH_SAME_DEVICE=1 GS_RCCL_LIB=$PWD/gaussian_splat_amd/librccl_stub.so timeout -k 10 600 python bench.py --gpus 2 --steps 10 --warmup 3 --cpu-baseline 0 --pmc 0 > $O/rehearsal_2rank_group_stub.json 2> $O/rehearsal_2rank_group_stub.err"
        cat $O/rehearsal_2rank_group_stub.json ;;
 scaling) step scaling bash tools/gpu_scaling.sh
        mkdir -p $O/scaling && cp gpurun_out/scaling/* $O/scaling/ ;;
