@@ -305,7 +305,9 @@ __global__ __launch_bounds__(256, (EPI == 2 && DEG == 3) ? 7 : GS_PRE_WAVES) voi
             l2 = fmaxf(l2, 0.0f);
             float r1 = 3.0f * sqrtf(l1);
             float r2 = 3.0f * sqrtf(l2);
-            if (r1 > 0.0f && r2 > 0.0f) {
+            // (a zero-area quad covers no pixel: a zero radius, or axes that
+            // normalised to (0, 0) where |(l1 - c, b)|^2 overflowed, tile.metal:78,143)
+            if (r1 > 0.0f && r2 > 0.0f && (e1x != 0.0f || e1y != 0.0f)) {
                 float W_ = (float)U.width, H_ = (float)U.height;
                 float ndcx = clx * invw, ndcy = cly * invw;
                 float cx = (ndcx + 1.0f) * (W_ * 0.5f);

@@ -554,7 +554,10 @@ void ora_project(const ora_scene *s, int64_t i, const float V[16], const float P
     dbg->a = a; dbg->b = b; dbg->c = c;
     dbg->r1 = r1; dbg->r2 = r2;
     dbg->e1x = e1x; dbg->e1y = e1y;
-    if (!(r1 > 0.0f && r2 > 0.0f)) return; /* zero-area quad covers no pixel */
+    /* a zero-area quad covers no pixel: a zero radius, or axes that normalised
+     * to (0, 0) because |(l1 - c, b)|^2 overflowed (tile.metal:78,143: all four
+     * corners then lie on the centre) */
+    if (!(r1 > 0.0f && r2 > 0.0f && (e1x != 0.0f || e1y != 0.0f))) return;
 
     /* K5/K6 closed form: centre in window px, uv scales. */
     float ndcx = clx * invw, ndcy = cly * invw;
@@ -619,11 +622,14 @@ void ora_project_all(const ora_scene *s, const float V[16], const float P[16], i
 /* F1 + S1 + A1: per-pixel composite                                        */
 /* ------------------------------------------------------------------------ */
 
-/* Coverage + gaussian of record j at pixel (px,py): returns alpha or -1.
+/* Coverage + gaussian of record j at pixel (px,py): returns whether the pixel
+ * is covered and then its alpha in *alpha.  The alpha takes no part in the
+ * coverage (tile.metal:187-197 discards on depth and on the gaussian only):
+ * it is whatever opacity * g gives, negative or NaN included.
  * The conic is staged per 16x16 tile (the composite kernel's workgroup):
  * scaled by sqrt(log2(e)/2), offset at the tile origin (tx0, ty0); the pixel
  * centre enters tile-local, (lx, ly) = (px - tx0 + 1/2, py - ty0 + 1/2). */
-static float frag_alpha(const ora_record *r, int px, int py) {
+static int frag_alpha(const ora_record *r, int px, int py, float *alpha) {
     int tx0 = px & ~(TILE - 1), ty0 = py & ~(TILE - 1);
     float ax = r->ax * ORA_CONIC_S, ay = r->ay * ORA_CONIC_S;
     float bx = r->bx * ORA_CONIC_S, by = r->by * ORA_CONIC_S;
@@ -632,10 +638,11 @@ static float frag_alpha(const ora_record *r, int px, int py) {
     float lx = (float)(px - tx0) + 0.5f, ly = (float)(py - ty0) + 0.5f;
     float u = fmaf(ax, lx, fmaf(-ay, ly, u0));
     float v = fmaf(bx, lx, fmaf(-by, ly, v0));
-    if (!(fmaxf(fabsf(u), fabsf(v)) <= ORA_BOXS)) return -1.0f; /* K6 quad coverage |uv| <= 3 */
+    if (!(fmaxf(fabsf(u), fabsf(v)) <= ORA_BOXS)) return 0; /* K6 quad coverage |uv| <= 3 */
     float q = fmaf(v, v, u * u);
-    if (!(q <= ORA_QMAXS)) return -1.0f; /* g < 0.01 discard, tile.metal:193 */
-    return r->opacity * ora_gauss2(q); /* tile.metal:197 */
+    if (!(q <= ORA_QMAXS)) return 0; /* g < 0.01 discard, tile.metal:193 */
+    *alpha = r->opacity * ora_gauss2(q); /* tile.metal:197 */
+    return 1;
 }
 
 typedef struct {
@@ -883,8 +890,8 @@ static int composite_records_impl(const ora_record *rec, const uint32_t *dkey, i
                         mlab_clear(&kb);
                         for (int64_t k = 0; k < m; ++k) {
                             const ora_record *r = &rec[ord[k].idx];
-                            float al = frag_alpha(r, px, py);
-                            if (al < 0.0f) continue;
+                            float al;
+                            if (!frag_alpha(r, px, py, &al)) continue;
                             mlab_insert(&kb, r->r, r->g, r->b, al, half_from_bits(0x7C00u - ord[k].key));
                         }
                         mlab_resolve(&kb, o);
@@ -899,8 +906,8 @@ static int composite_records_impl(const ora_record *rec, const uint32_t *dkey, i
                             if (!(T <= ORA_TSAT))
                                 for (int64_t k = 0; k < m; ++k) {
                                     const ora_record *r = &rec[ord[k].idx];
-                                    float al = frag_alpha(r, px, py);
-                                    if (al < 0.0f) continue;
+                                    float al;
+                                    if (!frag_alpha(r, px, py, &al)) continue;
                                     float sa = al * T;
                                     C0 = fmaf(r->r, sa, C0);
                                     C1 = fmaf(r->g, sa, C1);
@@ -912,8 +919,8 @@ static int composite_records_impl(const ora_record *rec, const uint32_t *dkey, i
                             if (!(T < ORA_TMIN))
                                 for (int64_t k = 0; k < m; ++k) {
                                     const ora_record *r = &rec[ord[k].idx];
-                                    float al = frag_alpha(r, px, py);
-                                    if (al < 0.0f) continue;
+                                    float al;
+                                    if (!frag_alpha(r, px, py, &al)) continue;
                                     C0 = fmaf(r->r, T, C0);
                                     C1 = fmaf(r->g, T, C1);
                                     C2 = fmaf(r->b, T, C2);
@@ -933,8 +940,8 @@ static int composite_records_impl(const ora_record *rec, const uint32_t *dkey, i
                             float T = 1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f; /* T = 1 - A */
                             for (int64_t k = 0; k < m; ++k) {
                                 const ora_record *r = &rec[ord[k].idx];
-                                float al = frag_alpha(r, px, py);
-                                if (al < 0.0f) continue;
+                                float al;
+                                if (!frag_alpha(r, px, py, &al)) continue;
                                 float sa = al * T;
                                 C0 = fmaf(r->r, sa, C0);
                                 C1 = fmaf(r->g, sa, C1);
@@ -947,8 +954,8 @@ static int composite_records_impl(const ora_record *rec, const uint32_t *dkey, i
                         }
                         for (int64_t k = 0; k < m; ++k) {
                             const ora_record *r = &rec[ord[k].idx];
-                            float al = frag_alpha(r, px, py);
-                            if (al < 0.0f) continue;
+                            float al;
+                            if (!frag_alpha(r, px, py, &al)) continue;
                             fr[c * 4 + 0] = r->r; fr[c * 4 + 1] = r->g; fr[c * 4 + 2] = r->b;
                             fr[c * 4 + 3] = al;
                             c++;
@@ -959,14 +966,15 @@ static int composite_records_impl(const ora_record *rec, const uint32_t *dkey, i
                         int ns = 0;
                         for (int64_t k = 0; k < m && ns < cap; ++k) {
                             const ora_record *r = &rec[ord[k].idx];
-                            if (frag_alpha(r, px, py) < 0.0f) continue;
+                            float al;
+                            if (!frag_alpha(r, px, py, &al)) continue;
                             sel[ns++] = ord[k];
                         }
                         qsort(sel, (size_t)ns, sizeof(kv), kv_cmp);
                         for (int k = 0; k < ns; ++k) {
                             const ora_record *r = &rec[sel[k].idx];
                             fr[c * 4 + 0] = r->r; fr[c * 4 + 1] = r->g; fr[c * 4 + 2] = r->b;
-                            fr[c * 4 + 3] = frag_alpha(r, px, py);
+                            (void)frag_alpha(r, px, py, &fr[c * 4 + 3]); /* (covered: it was selected) */
                             c++;
                         }
                     }
