@@ -14,11 +14,12 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <functional>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../kernels/gs_kernels.h"
@@ -44,49 +45,24 @@ gs_status fail(gs_status s, const std::string& msg) {
                         std::string(#expr) + ": " + hipGetErrorString(e_));                        \
     } while (0)
 
-#ifndef GS_DUP_FILTER_COUNT  // A/B knob: 1 = a depth-cut frame's duplicate counts the filtered pass's digits
-#define GS_DUP_FILTER_COUNT 0
-#endif
-#ifndef GS_DUP_FLAG  // A/B knob: 1 = the bin-first duplicate marks the pairs behind their cut (kBehindFlag)
-#define GS_DUP_FLAG 1
-#endif
-#ifndef GS_CUT_DILATE_AHEAD  // A/B knob: 1 = the next frame's dilated cuts are made by this frame's tail
-#define GS_CUT_DILATE_AHEAD 1
-#endif
-#ifndef GS_FB_LDS  // A/B knob: 1 = the fallback lists' filter tests an LDS copy of its table
-#define GS_FB_LDS 1
-#endif
-#ifndef GS_HOST_POLL  // A/B knob: 1 = the host polls the pair count's sequence word instead of an event
-#define GS_HOST_POLL 0
-#endif
-#ifndef GS_HOST_SET_WAIT  // A/B knob: 1 = the host waits for a buffer set's last reader (no GPU wait packet)
-#define GS_HOST_SET_WAIT 1
-#endif
-#ifndef GS_BAND_LOCAL  // A/B knob: 1 = contiguous band frames bin without an owner table (gs_handle::band_local)
-#define GS_BAND_LOCAL 1
-#endif
-#ifndef GS_DUP_FRONT  // A/B knob: 1 = a bin-first depth-cut frame emits only its front pairs (launch_front_count)
-#define GS_DUP_FRONT 1
-#endif
-#ifndef GS_DUP_FRONT_DILATED  // A/B knob: 1 = front-only emission also while the set's cuts are dilated (moving camera)
-#define GS_DUP_FRONT_DILATED 0
-#endif
-#ifndef GS_AUX_TOTALS  // A/B knob: 1 = a look-back frame's totals kernel runs on a stream of its own, beside the duplicate
-#define GS_AUX_TOTALS 1
-#endif
-#ifndef GS_AUX_ALL  // A/B knob: 1 = every depth-cut frame (not only front-only ones) gets look-back + aux totals
-#define GS_AUX_ALL 0
-#endif
-#ifndef GS_DUP_LOOKBACK  // A/B knob: 1 = the front-only duplicate finds its offsets by look-back (no count kernel)
-#define GS_DUP_LOOKBACK 1
-#endif
-#ifndef GS_DUP_FRONT_COUNT  // A/B knob: 1 = the front-only duplicate counts the first sort pass's digits
-#define GS_DUP_FRONT_COUNT 1
-#endif
-
+// A device allocation that frees itself; movable (the source is left empty),
+// not copyable.
 struct DevBuf {
     void* ptr = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : ptr(std::exchange(o.ptr, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            ptr = std::exchange(o.ptr, nullptr);
+            bytes = std::exchange(o.bytes, 0);
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     void release() {
         if (ptr) (void)hipFree(ptr);
         ptr = nullptr;
@@ -104,6 +80,14 @@ struct DevBuf {
     }
     template <typename T>
     T* as() const { return static_cast<T*>(ptr); }
+};
+static_assert(!std::is_copy_constructible_v<DevBuf>);
+
+// The buffers a frame's composite reads: one set per frame in flight
+// (gs_handle::cur / other, swap_sets).
+struct BufSet {
+    DevBuf rec, dkey, keys, vals, tkeys, tvals, ranges, thr, rlo, rhi;
+    DevBuf qrec, fkeys, fvals;  // depth cuts: quadrant records, front lists (gs_handle::cutbuf)
 };
 
 using gsio::sh_coeffs;
@@ -125,7 +109,7 @@ struct gs_handle {
     bool initialized = false;
     DevBuf p0, p1, p2, p3, sh4, sh1;
     // per-frame scratch
-    DevBuf rec, dkey, rlo, rhi, offsets, partials, keys, vals, tkeys, tvals, sort_scratch, ranges, fb, thr;
+    DevBuf offsets, partials, sort_scratch, fb;
     DevBuf dsk, dso, dsl, dsh, dtk, dto, dtl, dth;  // depth sort: keys, order, rect lo/hi (+ ping-pong)
     DevBuf xmask, xcounts, xtotal;  // multi-GPU exchange
     // depth-slab frames: full-frame ownership; the colour pass
@@ -164,7 +148,7 @@ struct gs_handle {
     int stats_set = -1;                 // buffer set of the frame in `stats` (its fetch counter)
     int64_t stats_fixed_bytes = 0;      // composite bytes besides the records: range words + output
     hipEvent_t totals_ev = nullptr;     // P is in host_total
-    hipStream_t aux = nullptr;          // (GS_AUX_TOTALS) a look-back frame's totals kernel
+    hipStream_t aux = nullptr;          // a look-back frame's totals kernel, beside the duplicate
     // gs_shard_render_split: the rank render's composite on a stream of its
     // own; comp_done follows its tail, the next rank render's lists wait for
     // it; the projection then leaves the fetch counters to the render
@@ -172,7 +156,6 @@ struct gs_handle {
     bool split_render = false;
     hipEvent_t xcount_ev = nullptr;  // (pack_exchange) the destination counts are in host_xtotal
     hipEvent_t pre_ev = nullptr;        // recorded by that frame's preprocess dispatch
-    unsigned long long totals_seq = 0;  // (GS_HOST_POLL) the last totals kernel's sequence number, host_total[5]
     struct OrderModel {                 // inputs of the binning-order choice (bin_first_order)
         int32_t w = 0, h = 0;
         int64_t n = -1;
@@ -208,14 +191,14 @@ struct gs_handle {
     DevBuf owner_dev, rows_dev;
     gs::CompositeArgs slab_ca{};
     // frames_in_flight 2: projection/sort stream, and the second set of the
-    // buffers a frame's composite reads (swapped into the members above)
+    // buffers a frame's composite reads (cur: the frame being enqueued;
+    // other: the frame before it; swap_sets)
     hipStream_t side = nullptr;
     hipEvent_t sorted_ev = nullptr;        // side stream -> composite stream hand-off
     hipEvent_t set_free[2] = {};           // last use of each buffer set on a composite stream
     int set = 0;
     bool last_pipe = false;  // the last frame ran pipelined (a switch into pipelining waits for the caller's stream)
-    DevBuf alt_rec, alt_dkey, alt_keys, alt_vals, alt_tkeys, alt_tvals, alt_ranges, alt_thr, alt_rlo, alt_rhi,
-        alt_qrec, alt_fkeys, alt_fvals;
+    BufSet cur, other;
     // Depth cuts (gs_options.depth_split).  cutbuf, per buffer
     // set, two per-bin cut tables: a frame's front lists keep the pairs at or
     // ahead of the cuts its set's previous frame (two frames back) left in
@@ -237,7 +220,7 @@ struct gs_handle {
     // kCutCalm frames with none.  dil_r: the radius of the set's table in
     // cutdil dilated ahead, by the tail of the frame that wrote the cuts (on
     // the composite stream, off the next frame's critical path); 0 = none.
-    DevBuf qrec, cutbuf, cutord, cutdil, wcost, cstate, fkeys, fvals, fbtab, fbn, scratch2, kept;
+    DevBuf cutbuf, cutord, cutdil, wcost, cstate, fbtab, fbn, scratch2, kept;
     int cut_r[2] = {0, 0};
     int cut_calm[2] = {0, 0};
     int dil_r[2] = {0, 0};
@@ -262,32 +245,16 @@ struct gs_handle {
         return cutord.as<uint32_t>() + (size_t)(2 * set + ((cut_phase[set] + role) & 1)) * cut_bins;
     }
     void swap_sets() {
-        std::swap(rec, alt_rec);
-        std::swap(dkey, alt_dkey);
-        std::swap(keys, alt_keys);
-        std::swap(vals, alt_vals);
-        std::swap(tkeys, alt_tkeys);
-        std::swap(tvals, alt_tvals);
-        std::swap(ranges, alt_ranges);
-        std::swap(thr, alt_thr);
-        std::swap(rlo, alt_rlo);
-        std::swap(rhi, alt_rhi);
-        std::swap(qrec, alt_qrec);
-        std::swap(fkeys, alt_fkeys);
-        std::swap(fvals, alt_fvals);
+        std::swap(cur, other);
         set ^= 1;
     }
     int64_t index_base = 0;
 
     ~gs_handle() {
-        for (DevBuf* b : {&p0, &p1, &p2, &p3, &sh4, &sh1, &rec, &dkey, &rlo, &rhi, &offsets, &partials, &keys,
-                          &vals, &tkeys, &tvals, &sort_scratch, &ranges, &fb, &thr, &dsk, &dso, &dsl, &dsh, &dtk, &dto,
-                          &dtl, &dth, &xmask, &xcounts, &xtotal, &owner_dev, &rows_dev, &alt_rec,
-                          &alt_dkey, &alt_keys, &alt_vals, &alt_tkeys, &alt_tvals, &alt_ranges, &alt_thr, &alt_rlo,
-                          &alt_rhi, &alt_qrec, &alt_fkeys, &alt_fvals, &seg_sample, &npairs, &fetch, &qrec, &cutbuf,
-                          &cstate, &fkeys, &fvals, &fbtab, &fbn, &scratch2, &kept, &ppart, &cutord, &cutdil, &wcost,
-                          &fbpart, &fbtot})
-            b->release();
+        // (the device buffers are DevBuf members: they free themselves after
+        // this body, once the streams, events and pinned memory are gone.  The
+        // device drains first, so none of those goes while a kernel uses it.)
+        if (initialized) (void)hipDeviceSynchronize();
         if (side) (void)hipStreamDestroy(side);
         if (sorted_ev) (void)hipEventDestroy(sorted_ev);
         if (totals_ev) (void)hipEventDestroy(totals_ev);
@@ -479,10 +446,10 @@ gs_status check_ready(gs_handle* h) {
 
 gs_status ensure_frame_scratch(gs_handle* h) {
     const size_t n = (size_t)std::max<int64_t>(h->n, 1);
-    GS_HIP(h->rec.reserve(n * gs::kRecFloat4 * 16));
-    GS_HIP(h->dkey.reserve(n * 4));
-    GS_HIP(h->rlo.reserve(n * 4));
-    GS_HIP(h->rhi.reserve(n * 4));
+    GS_HIP(h->cur.rec.reserve(n * gs::kRecFloat4 * 16));
+    GS_HIP(h->cur.dkey.reserve(n * 4));
+    GS_HIP(h->cur.rlo.reserve(n * 4));
+    GS_HIP(h->cur.rhi.reserve(n * 4));
     GS_HIP(h->partials.reserve(((n + gs::kScanItems - 1) / gs::kScanItems + 1) * 24));  // (3 rows: depth-cut front lists)
     if (!h->host_total) {  // written by the scan kernel itself, read after the stream sync
         GS_HIP(hipHostMalloc((void**)&h->host_total, 128, hipHostMallocMapped | hipHostMallocCoherent));
@@ -611,15 +578,15 @@ uint32_t reserve_pairs(gs_handle* h, uint64_t want) {
     // (depth-cut frames: the front lists in their own pair buffers)
     const bool cut = h->cut_pending;
     auto smallest = [&]() {
-        size_t m = std::min({h->keys.bytes, h->vals.bytes, h->tkeys.bytes, h->tvals.bytes});
-        return cut ? std::min({m, h->fkeys.bytes, h->fvals.bytes}) : m;
+        size_t m = std::min({h->cur.keys.bytes, h->cur.vals.bytes, h->cur.tkeys.bytes, h->cur.tvals.bytes});
+        return cut ? std::min({m, h->cur.fkeys.bytes, h->cur.fvals.bytes}) : m;
     };
     // growing frees the set's buffers: its last composite must be done
     if (p > smallest() && hipEventSynchronize(h->set_free[h->set]) != hipSuccess) return 0;
-    for (DevBuf* b : {&h->keys, &h->vals, &h->tkeys, &h->tvals})
+    for (DevBuf* b : {&h->cur.keys, &h->cur.vals, &h->cur.tkeys, &h->cur.tvals})
         if (b->reserve(p) != hipSuccess) return 0;
     if (cut)
-        for (DevBuf* b : {&h->fkeys, &h->fvals})
+        for (DevBuf* b : {&h->cur.fkeys, &h->cur.fvals})
             if (b->reserve(p) != hipSuccess) return 0;
     const size_t c = smallest() / 4;
     const uint32_t cap = (uint32_t)std::min<size_t>(c, UINT32_MAX - 1);
@@ -649,7 +616,7 @@ gs::PassCounts pass_counts(gs_handle* h, uint32_t m, bool index_order, const gs:
 gs_status prepare_lists(gs_handle* h, uint32_t m, bool index_order, const gs::FrameUniforms& U,
                         gs_handle::ListPrep* lp) {
     const uint32_t T = (uint32_t)(U.tiles_x * U.tiles_y);
-    GS_HIP(h->ranges.reserve((size_t)std::max<uint32_t>(T, 1) * sizeof(uint2)));
+    GS_HIP(h->cur.ranges.reserve((size_t)std::max<uint32_t>(T, 1) * sizeof(uint2)));
     if (!index_order) GS_HIP(h->offsets.reserve((size_t)std::max<uint32_t>(m, 1) * 4));
     lp->cap = reserve_pairs(h, h->order.frame_pairs);
     if (!lp->cap) return fail(GS_ERR_OOM, "pair buffers");
@@ -684,23 +651,6 @@ bool pick_bin_first(gs_handle* h, const gs::FrameUniforms& U, uint32_t m, int nr
 // tail (optional): queues what reads the lists (per-bin sort, composite ...)
 // right behind them, before the host waits for P, so that the GPU never waits
 // for the host; called again, with the lists, if they are queued again.
-// Waits until the totals kernel has published sequence number `seq` in
-// host_total[5] (its release store follows total[0..4]).  The kernel is a few
-// microseconds behind the projection, so the host spins; past a second it
-// falls back to a stream sync (an error if the word still differs).
-hipError_t wait_totals(gs_handle* h, unsigned long long seq, hipStream_t st) {
-    volatile unsigned long long* w = reinterpret_cast<volatile unsigned long long*>(h->host_total) + 5;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t spin = 0;; ++spin) {
-        if (__atomic_load_n(reinterpret_cast<const unsigned long long*>(h->host_total) + 5, __ATOMIC_ACQUIRE) == seq)
-            return hipSuccess;
-        if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(1)) break;
-    }
-    const hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return e;
-    return *w == seq ? hipSuccess : hipErrorUnknown;
-}
-
 using ListTail = std::function<gs_status(const uint32_t* sorted_vals)>;
 gs_status build_bin_lists(gs_handle* h, uint32_t m, const uint32_t* order, const uint32_t* rect_lo,
                           const uint32_t* rect_hi, const gs::FrameUniforms& U, const Ownership& own, bool timed,
@@ -732,29 +682,24 @@ gs_status build_bin_lists(gs_handle* h, uint32_t m, const uint32_t* order, const
         flt.bmask = (1u << bits) - 1u;
         flt.dshift = bits;
         flt.kept = h->kept.as<uint32_t>() + h->set;
-        pc.cut = h->cut_in;  // (the duplicate counts only the pairs the filtered first pass keeps)
-#if !GS_DUP_FILTER_COUNT
-        pc = gs::PassCounts{};
-#endif
+        pc = gs::PassCounts{};  // (the filtered first pass counts its own digits; front-only frames below)
         // the duplicate marks the pairs behind the cut from an LDS copy of the
         // table, so the filtered pass and its count test a bit instead of
         // gathering cut[bin] per pair (index order, every bin row owned)
-        flt.flag = GS_DUP_FLAG && !order && !own.dev.owner && T <= gs::kDupCutBins &&
+        flt.flag = !order && !own.dev.owner && T <= gs::kDupCutBins &&
                    bits + gs::kDepthBits <= 31 ? 1u : 0u;
         // (front-only frames count the first pass's digits in the duplicate:
         // its pairs are few and nearly all kept)
         if (front) flt.flag = 1u;
-        if (front && GS_DUP_FRONT_COUNT) pc = lp.pc;
+        if (front) pc = lp.pc;
     }
     h->front_last = front;
-    // (front-only, GS_DUP_LOOKBACK: no count kernel; the duplicate's blocks
-    // count their front pairs and find their offsets by look-back)
+    // (front-only: no count kernel; the duplicate's blocks count their front
+    // pairs and find their offsets by look-back)
     // (and every depth-cut frame whose totals run beside the duplicate, lp.aux)
-    const bool lookb = fused && GS_DUP_LOOKBACK && (front || lp.aux);
-    // the host learns P by polling the totals kernel's sequence word in
-    // host-mapped memory (GS_HOST_POLL) or by an event in its dispatch packet
-    const unsigned long long seq = GS_HOST_POLL ? ++h->totals_seq : 0ull;
-    hipEvent_t tev = GS_HOST_POLL ? nullptr : h->totals_ev;
+    const bool lookb = fused && (front || lp.aux);
+    // the host learns P by an event in the totals kernel's dispatch packet
+    hipEvent_t tev = h->totals_ev;
     if (fused) {
         const uint32_t nb = (m + gs::kScanItems - 1) / gs::kScanItems;
         if (front && !lookb)  // the front pairs' block sums into ppart's fourth row
@@ -767,18 +712,18 @@ gs_status build_bin_lists(gs_handle* h, uint32_t m, const uint32_t* order, const
             // preprocess is queued, which adds into ppart again
             GS_HIP(hipStreamWaitEvent(h->aux, h->pre_ev, 0));
             GS_HIP(gs::launch_scan_partials_fused(h->ppart.as<unsigned long long>(), nb, nullptr, h->dev_total,
-                                                  nullptr, nullptr, cap, h->aux, tev, seq, front, lookb));
+                                                  nullptr, nullptr, cap, h->aux, tev, front, lookb));
         } else {
             GS_HIP(gs::launch_scan_partials_fused(h->ppart.as<unsigned long long>(), nb, h->partials.as<uint64_t>(),
                                                   h->dev_total, h->seg_sample.as<uint32_t>() + 2 * h->set, np, cap,
-                                                  st, tev, seq, front, lookb));
+                                                  st, tev, front, lookb));
         }
         h->ppart_dirty = false;
     } else {
         GS_HIP(gs::launch_tile_count_totals(rect_lo, rect_hi, m, own.dev, U.cell_mask != 0, h->partials.as<uint64_t>(),
                                             h->dev_total, h->seg_sample.as<uint32_t>() + 2 * h->set,
-                                            h->ranges.as<uint2>(), T, np, cap, pc.C,
-                                            pc.C ? (pc.mask + 1) * pc.ntiles : 0u, st, tev, seq));
+                                            h->cur.ranges.as<uint2>(), T, np, cap, pc.C,
+                                            pc.C ? (pc.mask + 1) * pc.ntiles : 0u, st, tev));
     }
     if (timed) mark(h, 3, st);
     // pairs (bin, splat) in visiting order (bin-first: the depth key above the
@@ -788,7 +733,7 @@ gs_status build_bin_lists(gs_handle* h, uint32_t m, const uint32_t* order, const
     auto enqueue_lists = [&]() -> hipError_t {
         hipError_t e = gs::launch_scan_duplicate(order, rect_lo, rect_hi, h->partials.as<uint64_t>(), m,
                                                  (uint32_t)U.tiles_x, own.dev, U.cell_mask != 0, carry_dkey, bits,
-                                                 h->keys.as<uint32_t>(), h->vals.as<uint32_t>(),
+                                                 h->cur.keys.as<uint32_t>(), h->cur.vals.as<uint32_t>(),
                                                  np, st, h->offsets.as<uint32_t>(), pc,
                                                  flt.flag ? h->cut_in : nullptr, flt.flag ? T : 0u, front,
                                                  lookb ? np : nullptr, cap);
@@ -796,22 +741,22 @@ gs_status build_bin_lists(gs_handle* h, uint32_t m, const uint32_t* order, const
         if (timed) mark(h, 4, st);
         // (depth-cut frames: sorted into fkeys/fvals, so keys/vals keep every
         // pair for the fallback lists)
-        return gs::launch_radix_sort(h->keys.as<uint32_t>(), h->vals.as<uint32_t>(),
-                                     cut_frame ? h->fkeys.as<uint32_t>() : h->keys.as<uint32_t>(),
-                                     cut_frame ? h->fvals.as<uint32_t>() : h->vals.as<uint32_t>(),
-                                     h->tkeys.as<uint32_t>(), h->tvals.as<uint32_t>(), cap, bits,
-                                     h->sort_scratch.as<uint32_t>(), &in_tmp, st, h->ranges.as<uint2>(), np,
+        return gs::launch_radix_sort(h->cur.keys.as<uint32_t>(), h->cur.vals.as<uint32_t>(),
+                                     cut_frame ? h->cur.fkeys.as<uint32_t>() : h->cur.keys.as<uint32_t>(),
+                                     cut_frame ? h->cur.fvals.as<uint32_t>() : h->cur.vals.as<uint32_t>(),
+                                     h->cur.tkeys.as<uint32_t>(), h->cur.tvals.as<uint32_t>(), cap, bits,
+                                     h->sort_scratch.as<uint32_t>(), &in_tmp, st, h->cur.ranges.as<uint2>(), np,
                                      pc.C != nullptr, flt);
     };
     auto lists_done = [&]() -> gs_status {
-        uint32_t* fk = cut_frame ? h->fkeys.as<uint32_t>() : h->keys.as<uint32_t>();
-        uint32_t* fv = cut_frame ? h->fvals.as<uint32_t>() : h->vals.as<uint32_t>();
-        uint32_t* sk = in_tmp ? h->tkeys.as<uint32_t>() : fk;
-        uint32_t* sv = in_tmp ? h->tvals.as<uint32_t>() : fv;
+        uint32_t* fk = cut_frame ? h->cur.fkeys.as<uint32_t>() : h->cur.keys.as<uint32_t>();
+        uint32_t* fv = cut_frame ? h->cur.fvals.as<uint32_t>() : h->cur.vals.as<uint32_t>();
+        uint32_t* sk = in_tmp ? h->cur.tkeys.as<uint32_t>() : fk;
+        uint32_t* sv = in_tmp ? h->cur.tvals.as<uint32_t>() : fv;
         h->last_keys = sk;
         h->last_vals = sv;
-        h->last_tmp_keys = in_tmp ? fk : h->tkeys.as<uint32_t>();
-        h->last_tmp_vals = in_tmp ? fv : h->tvals.as<uint32_t>();
+        h->last_tmp_keys = in_tmp ? fk : h->cur.tkeys.as<uint32_t>();
+        h->last_tmp_vals = in_tmp ? fv : h->cur.tvals.as<uint32_t>();
         h->last_key_bits = bits;
         h->pair_cap = cap;
         if (timed) mark(h, 5, st);
@@ -822,11 +767,7 @@ gs_status build_bin_lists(gs_handle* h, uint32_t m, const uint32_t* order, const
     GS_HIP(enqueue_lists());
     gs_status ts = lists_done();
     if (ts != GS_OK) return ts;
-    if (seq) {  // (the GPU goes on with the lists meanwhile)
-        GS_HIP(wait_totals(h, seq, st));
-    } else {
-        GS_HIP(hipEventSynchronize(h->totals_ev));
-    }
+    GS_HIP(hipEventSynchronize(h->totals_ev));  // (the GPU goes on with the lists meanwhile)
     // P: the pairs the duplicate writes; P_all: every pair of the frame (the
     // same unless front-only; the pair buffers hold P_all, so that the
     // fallback lists always fit)
@@ -866,16 +807,14 @@ gs_status build_bin_lists(gs_handle* h, uint32_t m, const uint32_t* order, const
                                   ((size_t)(m + gs::kScanItems - 1) / gs::kScanItems + 1) * 8, st));
         pc = pass_counts(h, m, order == nullptr, plan, cap, lookb ? P_all : P);
         if (cut_frame) pc.cut = h->cut_in;
-#if !GS_DUP_FILTER_COUNT
-        if (cut_frame && !(front && GS_DUP_FRONT_COUNT)) pc = gs::PassCounts{};
-#endif
+        if (cut_frame && !front) pc = gs::PassCounts{};
         if (pc.C) GS_HIP(hipMemsetAsync(pc.C, 0, (size_t)(pc.mask + 1) * pc.ntiles * 4, st));
         if (tail) GS_HIP(hipMemsetAsync(fetch_counter(h), 0, 16, st));  // (the no-op frame's composite counted into these)
         // the bin ranges empty again: the no-op frame's tail may have written
         // some (a front-only frame's fallback lists are regenerated from the
         // rects, not from the empty pair arrays), and the re-queued sort's
         // last pass writes only the bins its lists hold
-        GS_HIP(hipMemsetAsync(h->ranges.ptr, 0xFF, (size_t)T * sizeof(uint2), st));
+        GS_HIP(hipMemsetAsync(h->cur.ranges.ptr, 0xFF, (size_t)T * sizeof(uint2), st));
         GS_HIP(enqueue_lists());
         if ((ts = lists_done()) != GS_OK) return ts;
     }
@@ -896,19 +835,13 @@ hipError_t reserve_after(DevBuf& b, size_t bytes, hipStream_t st) {
 
 // Depth cuts apply to this frame's composite rule and size:
 // tile / live50 rules, no fragment cap, the depth key above the bin id.
-#ifndef GS_CUT_DILATE_MAX  // A/B knobs of the dilation controller
-#define GS_CUT_DILATE_MAX 3
-#endif
-#ifndef GS_CUT_OPEN_TOL
-#define GS_CUT_OPEN_TOL 0
-#endif
-constexpr int kCutDilateMax = GS_CUT_DILATE_MAX;  // bins (3: a 7x7 neighbourhood)
+constexpr int kCutDilateMax = 3;  // bins (3: a 7x7 neighbourhood)
 constexpr int kCutCalm = 8;       // frames with no open quadrant before the radius drops by one
 // open quadrants a frame may leave without widening the radius: a few cost the
 // fallback lists little (they run on the composite stream, off the next
 // frame's chain), a wider radius costs every bin's front list
 // (profiles/r05/ab_dilate_radius.txt)
-constexpr uint64_t kCutOpenTolerated = GS_CUT_OPEN_TOL;
+constexpr uint64_t kCutOpenTolerated = 0;
 
 bool cut_rule(const gs_handle* h, const gs::FrameUniforms& U) {
     return h->opt.cap == 0 && (h->opt.mode == GS_MODE_TILE || h->opt.mode == GS_MODE_LIVE50) &&
@@ -947,7 +880,7 @@ gs_status setup_cuts(gs_handle* h, const gs::FrameUniforms& U, bool cut_frame, h
         h->cut_bins = T;
         h->cut_valid[0] = h->cut_valid[1] = false;
     }
-    GS_HIP(h->qrec.reserve((size_t)T * gs::kQrecWords * 4));
+    GS_HIP(h->cur.qrec.reserve((size_t)T * gs::kQrecWords * 4));
     GS_HIP(reserve_after(h->cstate, (size_t)U.width * U.height * 16, st));
     h->cut_in = h->cut_valid[h->set] ? h->cut_table(h->set, 0) : nullptr;
     h->cut_out = h->cut_table(h->set, 1);
@@ -972,8 +905,6 @@ gs_status setup_cuts(gs_handle* h, const gs::FrameUniforms& U, bool cut_frame, h
                 h->cut_calm[S] = 0;
             }
         }
-        static const char* fixed_r = std::getenv("GS_CUT_DILATE");  // (A/B: a fixed radius)
-        if (fixed_r) h->cut_r[S] = std::max(0, std::atoi(fixed_r));
         // two dilated tables per set: the one this frame reads (dil_slot[S],
         // made ahead by the tail of the frame that wrote its cuts, or here)
         // and the one this frame's tail dilates ahead into, which therefore
@@ -981,7 +912,7 @@ gs_status setup_cuts(gs_handle* h, const gs::FrameUniforms& U, bool cut_frame, h
         // (build_bin_lists' pair-buffer regrowth)
         uint32_t* d = h->cutdil.as<uint32_t>() + (size_t)(2 * S + h->dil_slot[S]) * T;
         h->dil_wslot[S] = h->dil_slot[S] ^ 1;
-        if (h->cut_in && h->cut_r[S] > 0 && GS_CUT_DILATE_AHEAD && h->dil_r[S] >= h->cut_r[S]) {
+        if (h->cut_in && h->cut_r[S] > 0 && h->dil_r[S] >= h->cut_r[S]) {
             // dilated ahead by the tail of the frame that wrote these cuts
             // (a wider radius than the controller's now only moves pairs from
             // the fallback lists to the front lists: the same image)
@@ -1030,7 +961,7 @@ gs_status cut_tail(gs_handle* h, const gs::FrameUniforms& U, gs::CompositeArgs c
         fb.table = h->fbtab.as<uint32_t>();
         fb.n = h->fbn.as<uint32_t>();
         fb.kept = h->kept.as<uint32_t>() + 2 + h->set;
-        fb.ranges = h->ranges.as<uint2>();
+        fb.ranges = h->cur.ranges.as<uint2>();
         if (h->dev_total) fb.host_open = reinterpret_cast<unsigned long long*>(h->dev_total) + 6 + h->set;
     }
     GS_HIP(gs::launch_cut_finalize(ca.qrec, ca.vals, dkey, h->cut_out, T, (uint32_t)U.tiles_x, own, cut_margin(), sc,
@@ -1046,7 +977,7 @@ gs_status cut_tail(gs_handle* h, const gs::FrameUniforms& U, gs::CompositeArgs c
     // the composite stream, which has slack while the side stream's
     // projection and chain bound the frame (1080p); a stream of its own
     // measured no better (profiles/r05/ab_dilate_radius.txt).
-    if (GS_CUT_DILATE_AHEAD && h->cut_out && h->cut_r[h->set] > 0 && h->cutdil.bytes >= (size_t)4 * T * 4) {
+    if (h->cut_out && h->cut_r[h->set] > 0 && h->cutdil.bytes >= (size_t)4 * T * 4) {
         const int S = h->set;
         uint32_t* d = h->cutdil.as<uint32_t>() + (size_t)(2 * S + h->dil_wslot[S]) * T;
         GS_HIP(gs::launch_cut_dilate(h->cut_out, d, (uint32_t)U.tiles_x, (uint32_t)U.tiles_y, h->cut_r[S], sc));
@@ -1054,9 +985,6 @@ gs_status cut_tail(gs_handle* h, const gs::FrameUniforms& U, gs::CompositeArgs c
         h->dil_slot[S] = h->dil_wslot[S];  // (the set's next frame reads it; idempotent when queued twice)
     }
     if (!h->cut_in) return GS_OK;  // (whole lists: no quadrant can be left open)
-#ifdef GS_AB_NO_FALLBACK  // timing ablation build only: exact only while no quadrant is left open
-    return GS_OK;
-#endif
     const int bits = h->last_key_bits;
     const uint32_t cap = h->pair_cap;
     GS_HIP(reserve_after(h->scratch2, gs::radix_sort_scratch_words(cap) * 4, sc));
@@ -1070,8 +998,8 @@ gs_status cut_tail(gs_handle* h, const gs::FrameUniforms& U, gs::CompositeArgs c
     // and the kept keys go without it)
     if (bits + gs::kDepthBits <= 31) flt.kmask = ~gs::kBehindFlag;
     // (the table tested in LDS: every pair of the frame is tested against a
-    // few open bins; GS_FB_LDS=0: the global gather, A/B)
-    if (GS_FB_LDS && T <= gs::kDupCutBins) flt.lds_bins = T;
+    // few open bins)
+    if (T <= gs::kDupCutBins) flt.lds_bins = T;
     if (h->front_last) {
         // the fallback pairs regenerated into keys/vals (free: the front lists
         // were sorted out of them on the side stream before this composite
@@ -1082,7 +1010,7 @@ gs_status cut_tail(gs_handle* h, const gs::FrameUniforms& U, gs::CompositeArgs c
         GS_HIP(reserve_after(h->fbtot, 16 * 8, sc));
         GS_HIP(gs::launch_fallback_pairs(rect_lo, rect_hi, dkey, m, U.cell_mask != 0, (uint32_t)U.tiles_x, bits, fb.table,
                                          T, fb.open, h->fbpart.as<uint64_t>(), h->fbtot.as<uint64_t>(), fb.n, fb.kept,
-                                         cap, h->keys.as<uint32_t>(), h->vals.as<uint32_t>(), sc));
+                                         cap, h->cur.keys.as<uint32_t>(), h->cur.vals.as<uint32_t>(), sc));
         flt.behind = 0;
         flt.flag = 1u;
         flt.kmask = ~0u;
@@ -1093,19 +1021,19 @@ gs_status cut_tail(gs_handle* h, const gs::FrameUniforms& U, gs::CompositeArgs c
     // per tile of the frame's pairs)
     flt.stride_grid = 512;
     bool in_tmp = false;
-    uint32_t* fk = h->fkeys.as<uint32_t>();
-    uint32_t* fv = h->fvals.as<uint32_t>();
-    GS_HIP(gs::launch_radix_sort(h->keys.as<uint32_t>(), h->vals.as<uint32_t>(), fk, fv, h->tkeys.as<uint32_t>(),
-                                 h->tvals.as<uint32_t>(), cap, bits, h->scratch2.as<uint32_t>(), &in_tmp, sc,
-                                 h->ranges.as<uint2>(), fb.n, false, flt));
-    uint32_t* sk = in_tmp ? h->tkeys.as<uint32_t>() : fk;
-    uint32_t* sv = in_tmp ? h->tvals.as<uint32_t>() : fv;
-    uint32_t* tk = in_tmp ? fk : h->tkeys.as<uint32_t>();
-    uint32_t* tv = in_tmp ? fv : h->tvals.as<uint32_t>();
-    GS_HIP(gs::launch_bin_depth_sort(h->ranges.as<uint2>(), T, sk, sv, tk, tv, bits, nullptr, sc, nullptr,
+    uint32_t* fk = h->cur.fkeys.as<uint32_t>();
+    uint32_t* fv = h->cur.fvals.as<uint32_t>();
+    GS_HIP(gs::launch_radix_sort(h->cur.keys.as<uint32_t>(), h->cur.vals.as<uint32_t>(), fk, fv,
+                                 h->cur.tkeys.as<uint32_t>(), h->cur.tvals.as<uint32_t>(), cap, bits,
+                                 h->scratch2.as<uint32_t>(), &in_tmp, sc, h->cur.ranges.as<uint2>(), fb.n, false, flt));
+    uint32_t* sk = in_tmp ? h->cur.tkeys.as<uint32_t>() : fk;
+    uint32_t* sv = in_tmp ? h->cur.tvals.as<uint32_t>() : fv;
+    uint32_t* tk = in_tmp ? fk : h->cur.tkeys.as<uint32_t>();
+    uint32_t* tv = in_tmp ? fv : h->cur.tvals.as<uint32_t>();
+    GS_HIP(gs::launch_bin_depth_sort(h->cur.ranges.as<uint2>(), T, sk, sv, tk, tv, bits, nullptr, sc, nullptr,
                                      open_counter(h)));
     ca.vals = sv;
-    ca.ranges = h->ranges.as<uint2>();
+    ca.ranges = h->cur.ranges.as<uint2>();
     ca.pass = 2;
     ca.fetched = nullptr;
     GS_HIP(gs::launch_composite(ca, h->opt.mode, sc));
@@ -1171,7 +1099,7 @@ gs_status bin_sort_composite(gs_handle* h, uint32_t m, const uint32_t* dkey, con
         gs_status s = build_bin_lists(h, m, nullptr, rect_lo, rect_hi, U, bown, true, st, &vals, &P);
         if (s != GS_OK) return s;
         ca.vals = vals;
-        ca.ranges = h->ranges.as<uint2>();
+        ca.ranges = h->cur.ranges.as<uint2>();
         GS_HIP(handoff());
         ca.fetched = fetch_counter(h);
         GS_HIP(gs::launch_composite(ca, h->opt.mode, sc, kernel_event(h, 2), kernel_event(h, 3)));
@@ -1203,7 +1131,7 @@ gs_status bin_sort_composite(gs_handle* h, uint32_t m, const uint32_t* dkey, con
         ca.fetched = fetch_counter(h);
         if (cutf) {
             ca.pass = 1;
-            ca.qrec = h->qrec.as<uint32_t>();
+            ca.qrec = h->cur.qrec.as<uint32_t>();
             ca.open_q_count = open_counter(h);
             ca.state = h->cstate.as<float4>();
             ca.cut_in = h->cut_in;
@@ -1216,17 +1144,17 @@ gs_status bin_sort_composite(gs_handle* h, uint32_t m, const uint32_t* dkey, con
         const ListTail tail = [&](const uint32_t* sv) -> gs_status {
             gs::CompositeArgs c = ca;
             c.vals = sv;
-            c.ranges = h->ranges.as<uint2>();
+            c.ranges = h->cur.ranges.as<uint2>();
             if (c.cap > 0) {  // per-pixel cap thresholds from the lists in arrival order
-                GS_HIP(h->thr.reserve((size_t)U.width * U.height * 4));
-                c.thr_out = h->thr.as<uint32_t>();
+                GS_HIP(h->cur.thr.reserve((size_t)U.width * U.height * 4));
+                c.thr_out = h->cur.thr.as<uint32_t>();
                 GS_HIP(gs::launch_cap_threshold(c, sd));
-                c.thr = h->thr.as<uint32_t>();
+                c.thr = h->cur.thr.as<uint32_t>();
             }
             // (one sample word pair per buffer set, for the binning-order
             // model; not from cut lists, whose short lists would understate
             // the per-bin sort of whole ones)
-            GS_HIP(gs::launch_bin_depth_sort(h->ranges.as<uint2>(), (uint32_t)(U.tiles_x * U.tiles_y), h->last_keys,
+            GS_HIP(gs::launch_bin_depth_sort(h->cur.ranges.as<uint2>(), (uint32_t)(U.tiles_x * U.tiles_y), h->last_keys,
                                              h->last_vals, h->last_tmp_keys, h->last_tmp_vals, h->last_key_bits,
                                              cutf && h->cut_in ? nullptr : h->seg_sample.as<uint32_t>() + 2 * h->set,
                                              sd, sc != st ? h->sorted_ev : nullptr, nullptr,
@@ -1258,14 +1186,14 @@ gs_status bin_sort_composite(gs_handle* h, uint32_t m, const uint32_t* dkey, con
     h->bin_first_frame = false;
     if (ca.cap > 0) {
         // 0. per-pixel cap thresholds from the lists in arrival (index) order
-        GS_HIP(h->thr.reserve((size_t)U.width * U.height * 4));
+        GS_HIP(h->cur.thr.reserve((size_t)U.width * U.height * 4));
         gs_status s = build_bin_lists(h, m, nullptr, rect_lo, rect_hi, U, bown, false, st, &vals, &P);
         if (s != GS_OK) return s;
         ca.vals = vals;
-        ca.ranges = h->ranges.as<uint2>();
-        ca.thr_out = h->thr.as<uint32_t>();
+        ca.ranges = h->cur.ranges.as<uint2>();
+        ca.thr_out = h->cur.thr.as<uint32_t>();
         GS_HIP(gs::launch_cap_threshold(ca, st));
-        ca.thr = h->thr.as<uint32_t>();
+        ca.thr = h->cur.thr.as<uint32_t>();
     }
     // 1. splats by depth (descending zF == ascending dkey), ties by index,
     //    carrying (index, rect) so everything downstream reads sequentially
@@ -1290,7 +1218,7 @@ gs_status bin_sort_composite(gs_handle* h, uint32_t m, const uint32_t* dkey, con
         const uint32_t* sdk = in_tmp ? h->dtk.as<uint32_t>() : h->dsk.as<uint32_t>();  // (dkeys in depth order)
         ca.fetched = fetch_counter(h);
         ca.pass = 1;
-        ca.qrec = h->qrec.as<uint32_t>();
+        ca.qrec = h->cur.qrec.as<uint32_t>();
         ca.open_q_count = open_counter(h);
         ca.state = h->cstate.as<float4>();
         ca.cut_in = h->cut_in;
@@ -1300,7 +1228,7 @@ gs_status bin_sort_composite(gs_handle* h, uint32_t m, const uint32_t* dkey, con
         const ListTail tail = [&](const uint32_t* sv) -> gs_status {
             gs::CompositeArgs c = ca;
             c.vals = sv;
-            c.ranges = h->ranges.as<uint2>();
+            c.ranges = h->cur.ranges.as<uint2>();
             mark(h, 6, st);
             GS_HIP(handoff());
             GS_HIP(gs::launch_composite(c, h->opt.mode, sc, kernel_event(h, 2), kernel_event(h, 3)));
@@ -1320,7 +1248,7 @@ gs_status bin_sort_composite(gs_handle* h, uint32_t m, const uint32_t* dkey, con
     gs_status s = build_bin_lists(h, m, order, slo, shi, U, bown, true, st, &vals, &P);
     if (s != GS_OK) return s;
     ca.vals = vals;
-    ca.ranges = h->ranges.as<uint2>();
+    ca.ranges = h->cur.ranges.as<uint2>();
     if (slab_t) {  // depth-slab transmittance pass; the colour pass reuses the lists
         ca.slab = 1;
         ca.t_out = slab_t;
@@ -1578,14 +1506,11 @@ gs_status gs_initialize(gs_handle* h, int32_t device) {
     // frames_in_flight 2: the side stream (projection .. per-bin sort, the
     // frame's critical path, HBM- and latency-bound) runs at the highest queue
     // priority, so the dispatcher prefers its workgroups and the overlapping
-    // composite (VALU-bound) fills the remaining slots.  GS_SIDE_PRIORITY=0:
-    // default priority (A/B).
+    // composite (VALU-bound) fills the remaining slots.
     int least = 0, greatest = 0;
     GS_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    const char* sp_env = std::getenv("GS_SIDE_PRIORITY");
-    const bool high = !(sp_env && sp_env[0] == '0');
-    GS_HIP(hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, high ? greatest : 0));
-    GS_HIP(hipStreamCreateWithPriority(&h->aux, hipStreamNonBlocking, high ? greatest : 0));
+    GS_HIP(hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, greatest));
+    GS_HIP(hipStreamCreateWithPriority(&h->aux, hipStreamNonBlocking, greatest));
     GS_HIP(hipEventCreateWithFlags(&h->pre_ev, hipEventDisableTiming));
     GS_HIP(hipEventCreateWithFlags(&h->comp_done, hipEventDisableTiming));
     GS_HIP(hipEventCreateWithFlags(&h->xcount_ev, hipEventDisableTiming));
@@ -1668,9 +1593,9 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
         if (own.dev.owner && (int)rows.back() - (int)rows.front() + 1 == (int)rows.size()) {
             U.band_y0 = (int32_t)rows.front() * gs::kBin;
             U.band_y1 = std::min(H, ((int32_t)rows.back() + 1) * gs::kBin) - 1;
-            h->band_local = GS_BAND_LOCAL != 0;
+            h->band_local = true;
         } else if (!own.dev.owner) {
-            h->band_local = GS_BAND_LOCAL != 0;  // (world 1: the band is the frame)
+            h->band_local = true;  // (world 1: the band is the frame)
         }
         compact = own.dev.owner ? 1 : 0;
         band_nrows = own.nrows;
@@ -1694,11 +1619,11 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
     // (a wait packet only when that composite may still run: each costs a
     // few us of stream bubble)
     if (hipEventQuery(h->set_free[h->set]) != hipSuccess) {
-        // (GS_HOST_SET_WAIT, A/B) the host waits instead of a wait packet in
-        // the side stream: the set's last composite ends with the co-run, long
-        // before the side stream finishes the previous frame's chain, so the
-        // projection is still queued in time and its stream has no barrier
-        if (GS_HOST_SET_WAIT && pipe) GS_HIP(hipEventSynchronize(h->set_free[h->set]));
+        // the host waits instead of a wait packet in the side stream: the
+        // set's last composite ends with the co-run, long before the side
+        // stream finishes the previous frame's chain, so the projection is
+        // still queued in time and its stream has no barrier
+        if (pipe) GS_HIP(hipEventSynchronize(h->set_free[h->set]));
         else GS_HIP(hipStreamWaitEvent(sp, h->set_free[h->set], 0));
     }
     if (h->split_render) {  // (a split rank render's composite may still count into this set's counters)
@@ -1715,15 +1640,13 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
     // block's pairs, fills the empty bin ranges and zeroes the first sort
     // pass's counts (PreFuse), so the chain starts at the scan of the block
     // sums.  The binning order and the list buffers are settled first.
-    // GS_FUSED_SCAN=0: the separate reduce pass (A/B).
-    static const char* fs_env = std::getenv("GS_FUSED_SCAN");
     gs::PreFuse fuse;
     h->fused_prep = gs_handle::ListPrep{};
     h->order_pick = -1;
     const bool whole = band ? h->band_local : h->world == 1;  // (the binning owns every row it sees)
     const bool cut_on = depth_cuts_on(h) && whole && cut_rule(h, U);
     bool cut_frame = false;
-    if (whole && h->n > 0 && h->opt.mode != GS_MODE_MLAB && !(fs_env && fs_env[0] == '0')) {
+    if (whole && h->n > 0 && h->opt.mode != GS_MODE_MLAB) {
         const bool bf = bin_first_order(h, U, (uint32_t)h->n, h->band_local ? band_nrows : -1, cut_on);
         h->order_pick = bf ? 1 : 0;
         cut_frame = cut_on;
@@ -1740,7 +1663,7 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
             }
             fuse.part = h->ppart.as<unsigned long long>();
             fuse.nb = nb;
-            fuse.fill = h->ranges.as<uint2>();
+            fuse.fill = h->cur.ranges.as<uint2>();
             fuse.nfill = T;
             // Front-only emission (a frame with cuts, the duplicate's table in
             // LDS, the behind mark above the depth key): the duplicate writes
@@ -1751,13 +1674,10 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
             // (not while the set's cuts are dilated: a moving camera leaves
             // quadrants open, and regenerating their fallback pairs from every
             // splat's rect costs more than the whole pairs' sort pass it saves)
-            h->fused_prep.front = GS_DUP_FRONT && h->cut_in && (GS_DUP_FRONT_DILATED || h->cut_r[h->set] == 0) &&
-                                  T <= gs::kDupCutBins &&
+            h->fused_prep.front = h->cut_in && h->cut_r[h->set] == 0 && T <= gs::kDupCutBins &&
                                   list_key_bits(U) + gs::kDepthBits <= 31;
             h->fused_prep.pc.cut = h->cut_in;  // (with cuts: the duplicate counts only the pairs the filter keeps)
-#if !GS_DUP_FILTER_COUNT
-            if (h->cut_in && !(h->fused_prep.front && GS_DUP_FRONT_COUNT)) h->fused_prep.pc = gs::PassCounts{};
-#endif
+            if (h->cut_in && !h->fused_prep.front) h->fused_prep.pc = gs::PassCounts{};
             fuse.zero = h->fused_prep.pc.C;
             fuse.nzero = h->fused_prep.pc.C ? (h->fused_prep.pc.mask + 1) * h->fused_prep.pc.ntiles : 0u;
             // (look-back frames: the preprocess clears the duplicate's statuses
@@ -1765,9 +1685,7 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
             // not while the preprocess's dispatch carries timing events)
             // (depth-cut frames only: the aux totals carry no per-bin sort
             // sample, which only frames without cuts use)
-            h->fused_prep.aux = GS_AUX_TOTALS && GS_DUP_LOOKBACK && cut_frame && h->cut_in && !kernel_event(h, 1) &&
-                                (h->fused_prep.front || (GS_AUX_ALL && T <= gs::kDupCutBins &&
-                                                         list_key_bits(U) + gs::kDepthBits <= 31));
+            h->fused_prep.aux = cut_frame && h->cut_in && !kernel_event(h, 1) && h->fused_prep.front;
             if (h->fused_prep.aux) {
                 fuse.zero64 = reinterpret_cast<unsigned long long*>(h->partials.as<uint64_t>());
                 fuse.nzero64 = nb + 1;
@@ -1777,12 +1695,13 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
         }
     }
     if (!cut_frame && (s = setup_cuts(h, U, false, st, sp)) != GS_OK) return s;
-    GS_HIP(gs::launch_preprocess(h->scene_dev(), h->opt.sh_degree, U, h->rec.as<float4>(), h->dkey.as<uint32_t>(),
-                                 h->rlo.as<uint32_t>(), h->rhi.as<uint32_t>(), sp, kernel_event(h, 0),
-                                 h->fused_prep.aux ? h->pre_ev : kernel_event(h, 1), fetch_counter(h), fuse));
+    GS_HIP(gs::launch_preprocess(h->scene_dev(), h->opt.sh_degree, U, h->cur.rec.as<float4>(),
+                                 h->cur.dkey.as<uint32_t>(), h->cur.rlo.as<uint32_t>(), h->cur.rhi.as<uint32_t>(), sp,
+                                 kernel_event(h, 0), h->fused_prep.aux ? h->pre_ev : kernel_event(h, 1),
+                                 fetch_counter(h), fuse));
     mark(h, 1, sp);
-    if ((s = bin_sort_composite(h, (uint32_t)h->n, h->dkey.as<uint32_t>(), h->rlo.as<uint32_t>(),
-                                h->rhi.as<uint32_t>(), h->rec.as<float4>(), gs::kRecFloat4, U, compact,
+    if ((s = bin_sort_composite(h, (uint32_t)h->n, h->cur.dkey.as<uint32_t>(), h->cur.rlo.as<uint32_t>(),
+                                h->cur.rhi.as<uint32_t>(), h->cur.rec.as<float4>(), gs::kRecFloat4, U, compact,
                                 bgra8 ? nullptr : static_cast<float4*>(out),
                                 bgra8 ? static_cast<uint32_t*>(out) : nullptr, sp, nullptr, &st)) != GS_OK)
         return s;
@@ -1898,13 +1817,13 @@ gs_status gs_project_host(gs_handle* h, const float* view, const float* proj, in
     const gs::FrameUniforms U = make_uniforms(view, proj, W, H);
     hipStream_t st = nullptr;
     GS_HIP(hipEventSynchronize(h->set_free[h->set]));  // a pipelined composite may still read the set
-    GS_HIP(gs::launch_preprocess(h->scene_dev(), h->opt.sh_degree, U, h->rec.as<float4>(), h->dkey.as<uint32_t>(),
-                                 h->rlo.as<uint32_t>(), h->rhi.as<uint32_t>(), st));
+    GS_HIP(gs::launch_preprocess(h->scene_dev(), h->opt.sh_degree, U, h->cur.rec.as<float4>(),
+                                 h->cur.dkey.as<uint32_t>(), h->cur.rlo.as<uint32_t>(), h->cur.rhi.as<uint32_t>(), st));
     GS_HIP(hipStreamSynchronize(st));
     const size_t n = (size_t)h->n;
     if (records) {
-        GS_HIP(hipMemcpy2D(records, sizeof(gs::Record3), h->rec.ptr, (size_t)gs::kRecFloat4 * 16, sizeof(gs::Record3),
-                           n, hipMemcpyDeviceToHost));
+        GS_HIP(hipMemcpy2D(records, sizeof(gs::Record3), h->cur.rec.ptr, (size_t)gs::kRecFloat4 * 16,
+                           sizeof(gs::Record3), n, hipMemcpyDeviceToHost));
         if (U.cell_mask) {  // the cell-exclusion mask is internal: export the reference record
             uint32_t* w = static_cast<uint32_t*>(records);
             for (size_t i = 0; i < n; ++i) {
@@ -1913,11 +1832,11 @@ gs_status gs_project_host(gs_handle* h, const float* view, const float* proj, in
             }
         }
     }
-    if (dkeys) GS_HIP(hipMemcpy(dkeys, h->dkey.ptr, n * 4, hipMemcpyDeviceToHost));
+    if (dkeys) GS_HIP(hipMemcpy(dkeys, h->cur.dkey.ptr, n * 4, hipMemcpyDeviceToHost));
     if (ntiles) {
         std::vector<uint32_t> lo(n), hi(n);
-        GS_HIP(hipMemcpy(lo.data(), h->rlo.ptr, n * 4, hipMemcpyDeviceToHost));
-        GS_HIP(hipMemcpy(hi.data(), h->rhi.ptr, n * 4, hipMemcpyDeviceToHost));
+        GS_HIP(hipMemcpy(lo.data(), h->cur.rlo.ptr, n * 4, hipMemcpyDeviceToHost));
+        GS_HIP(hipMemcpy(hi.data(), h->cur.rhi.ptr, n * 4, hipMemcpyDeviceToHost));
         const uint32_t cm = U.cell_mask ? 0x0FFF0FFFu : 0xFFFFFFFFu;  // strip the bin-exclusion mask
         for (size_t i = 0; i < n; ++i) {
             const uint32_t l = lo[i] & cm, u = hi[i] & cm;
@@ -2045,9 +1964,9 @@ gs_status shard_preprocess(gs_handle* h, const float* view, const float* proj, i
         sf.nblocks = (uint32_t)((h->n + gs::kShardItems - 1) / gs::kShardItems);
         if (sf.nblocks) GS_HIP(hipMemsetAsync(sf.counts, 0, (size_t)sf.nblocks * h->world * 4, st));
     }
-    GS_HIP(gs::launch_preprocess(h->scene_dev(), h->opt.sh_degree, *U, h->rec.as<float4>(), h->dkey.as<uint32_t>(),
-                                 h->rlo.as<uint32_t>(), h->rhi.as<uint32_t>(), st, kernel_event(h, 0),
-                                 kernel_event(h, 1), zero8, gs::PreFuse{}, sf));
+    GS_HIP(gs::launch_preprocess(h->scene_dev(), h->opt.sh_degree, *U, h->cur.rec.as<float4>(),
+                                 h->cur.dkey.as<uint32_t>(), h->cur.rlo.as<uint32_t>(), h->cur.rhi.as<uint32_t>(), st,
+                                 kernel_event(h, 0), kernel_event(h, 1), zero8, gs::PreFuse{}, sf));
     mark(h, 1, st);
     return GS_OK;
 }
@@ -2063,14 +1982,14 @@ gs_status pack_exchange(gs_handle* h, const gs::DestRule& rule, bool masked, voi
     // (the scan writes every destination's total; with no splats it does not run)
     if (nb == 0) GS_HIP(hipMemsetAsync(h->xtotal.ptr, 0, gs::kMaxWorld * 4, st));
     if (!counted)  // (counted: the projection wrote the masks and counts, ShardFuse)
-        GS_HIP(gs::launch_shard_count(h->rlo.as<uint32_t>(), h->rhi.as<uint32_t>(), n, h->world, rule, masked,
+        GS_HIP(gs::launch_shard_count(h->cur.rlo.as<uint32_t>(), h->cur.rhi.as<uint32_t>(), n, h->world, rule, masked,
                                       h->xmask.as<uint32_t>(), h->xcounts.as<uint32_t>(), nb, st));
     GS_HIP(gs::launch_rows_scan(h->xcounts.as<uint32_t>(), nb, nb ? h->world : 0, h->xtotal.as<uint32_t>(), st));
     GS_HIP(hipMemcpyAsync(h->host_xtotal, h->xtotal.ptr, h->world * 4, hipMemcpyDeviceToHost, st));
     GS_HIP(hipEventRecord(h->xcount_ev, st));
     auto pack = [&]() -> hipError_t {
-        return gs::launch_shard_pack(h->rec.as<float4>(), h->rlo.as<uint32_t>(), h->rhi.as<uint32_t>(),
-                                     h->dkey.as<uint32_t>(), h->xmask.as<uint32_t>(), n, h->world,
+        return gs::launch_shard_pack(h->cur.rec.as<float4>(), h->cur.rlo.as<uint32_t>(), h->cur.rhi.as<uint32_t>(),
+                                     h->cur.dkey.as<uint32_t>(), h->xmask.as<uint32_t>(), n, h->world,
                                      h->xcounts.as<uint32_t>(), h->xtotal.as<uint32_t>(), nb,
                                      static_cast<float4*>(send), st);
     };
@@ -2212,7 +2131,7 @@ gs_status gs_slab_project(gs_handle* h, const float* view, const float* proj, in
     gs_status s = shard_preprocess(h, view, proj, W, H, st, &U);
     if (s != GS_OK) return s;
     GS_HIP(hipMemsetAsync(hist, 0, (size_t)gs::kSlabBins * 8, st));
-    GS_HIP(gs::launch_slab_histogram(h->dkey.as<uint32_t>(), h->rlo.as<uint32_t>(), h->rhi.as<uint32_t>(),
+    GS_HIP(gs::launch_slab_histogram(h->cur.dkey.as<uint32_t>(), h->cur.rlo.as<uint32_t>(), h->cur.rhi.as<uint32_t>(),
                                      (uint32_t)h->n, U.cell_mask != 0,
                                      reinterpret_cast<unsigned long long*>(hist), st));
     h->slab_w = W;
@@ -2244,7 +2163,7 @@ gs_status gs_slab_pack(gs_handle* h, const uint32_t* bounds, void* send, int64_t
     if (!h || !bounds || !send_counts) return fail(GS_ERR_INVALID_ARG, "gs_slab_pack: bad arguments");
     if (!h->slab_frame || !h->shard_frame) return fail(GS_ERR_STATE, "gs_slab_pack: call gs_slab_project first");
     gs::DestRule rule{};
-    rule.dkey = h->dkey.as<uint32_t>();
+    rule.dkey = h->cur.dkey.as<uint32_t>();
     rule.slabs = 1;
     for (int d = 0; d <= h->world; ++d) {
         if (d > 0 && bounds[d] < bounds[d - 1]) return fail(GS_ERR_INVALID_ARG, "gs_slab_pack: bounds not ascending");

@@ -233,7 +233,7 @@ __device__ __forceinline__ void sort_list_global(uint32_t s, uint32_t m, uint32_
 #define GS_SEG_SMALL_MINW 6
 #endif
 
-// CLS (GS_SEG_CLASSES): 0 every list; 1 the lists of at most kSegSmallMax
+// CLS: 0 every list; 1 the lists of at most kSegSmallMax
 // pairs only; 2 the longer ones only (two launches over every bin, so that
 // short lists run in narrow workgroups, more bins at a time, and long ones
 // keep the wide workgroup's LDS capacity).
@@ -307,11 +307,7 @@ __global__ __launch_bounds__(NT, MINW) void bin_depth_sort_kernel(const uint2* _
 #pragma unroll
     for (int k = 0; k < IPT; ++k) {
         const uint32_t p = base + (uint32_t)k * 64u + lane;
-#ifdef GS_SEG_ABL_NOGATHER  // ablation (timing only): coalesced read of the own slot (ids stay valid)
-        v[k] = (k < kmax && p < m) ? vals[s + p] : 0u;
-#else
         v[k] = vals[s + ((k < kmax && p < m) ? (it[k] & ((1u << kSegPosBits) - 1u)) : 0u)];
-#endif
     }
 #pragma unroll
     for (int k = 0; k < IPT; ++k) asm volatile("" ::"v"(v[k]));  // loads complete before the barrier
@@ -337,7 +333,7 @@ hipError_t launch_bin_depth_sort(const uint2* ranges, uint32_t nbins, uint32_t* 
     // of ~2-3k pairs, more of them past the short class) keep one launch: the
     // long class alone then leaves the part idle (profiles/r06/ab_seg_classes.txt).
     static_assert(GS_SEG_SMALL_NT * GS_SEG_SMALL_IPT == kSegSmallMax && kSegSmallMax < kSegLdsMax, "gs_kernels.h");
-    if (GS_SEG_CLASSES && nbins >= (uint32_t)GS_SEG_CLASS_MIN_BINS) {
+    if (nbins >= (uint32_t)GS_SEG_CLASS_MIN_BINS) {
         hipExtLaunchKernelGGL((bin_depth_sort_kernel<GS_SEG_NT, GS_SEG_IPT, GS_SEG_MINW, 2>), dim3(nbins),
                               dim3(GS_SEG_NT), 0, st, nullptr, nullptr, 0, ranges, keys, vals, tmp_keys, tmp_vals,
                               bin_bits, sample, guard);
@@ -346,7 +342,7 @@ hipError_t launch_bin_depth_sort(const uint2* ranges, uint32_t nbins, uint32_t* 
                               tmp_vals, bin_bits, nullptr, guard);
         return hipGetLastError();
     }
-    if (GS_SEG_SHORT && short_lists) {  // (a still camera's front lists: every list in 256-lane workgroups)
+    if (short_lists) {  // (a still camera's front lists: every list in 256-lane workgroups)
         hipExtLaunchKernelGGL((bin_depth_sort_kernel<GS_SEG_SMALL_NT, GS_SEG_SMALL_IPT, GS_SEG_SMALL_MINW>), dim3(nbins),
                               dim3(GS_SEG_SMALL_NT), 0, st, nullptr, done, 0, ranges, keys, vals, tmp_keys, tmp_vals,
                               bin_bits, sample, guard);

@@ -490,23 +490,11 @@ __global__ __launch_bounds__(256, MODE == 3 ? 4 : 8) __attribute__((amdgpu_num_s
 //    its coverage test.
 // Staged slot (48 B): a = (Ax', -Ay', Bx', -By'), b = (opacity, r, g, b),
 // c = (U0, V0) at the left tile's origin, then at the right tile's.
-#ifndef GS_COMPOSITE_LPT  // A/B knob: 0 = row-major bin order even when CompositeArgs::order is set
-#define GS_COMPOSITE_LPT 1
-#endif
 #ifndef GS_STRIP_PRIO_TOP  // the first batches' issue priority (then one lower every two batches)
 #define GS_STRIP_PRIO_TOP 3
 #endif
-#ifndef GS_STRIP_PRIO  // A/B knob: 1 = issue priority falls with the batches a workgroup has walked
-#define GS_STRIP_PRIO 1
-#endif
-#ifndef GS_STRIP_PIPE  // A/B knob: 1 = the walk reads one record ahead (rolling), 0 = two records per step
-#define GS_STRIP_PIPE 1
-#endif
-#ifndef GS_STRIP_WAVES  // A/B knob: waves per SIMD the strip composite is built for
+#ifndef GS_STRIP_WAVES  // tunable: waves per SIMD the strip composite is built for
 #define GS_STRIP_WAVES 8
-#endif
-#ifndef GS_STRIP_PAD
-#define GS_STRIP_PAD 0
 #endif
 template <int MODE, int PASS>
 __global__ __launch_bounds__(256, GS_STRIP_WAVES) __attribute__((amdgpu_num_sgpr(GS_COMPOSITE_SGPRS))) void composite_strip_kernel(
@@ -516,10 +504,6 @@ __global__ __launch_bounds__(256, GS_STRIP_WAVES) __attribute__((amdgpu_num_sgpr
     __shared__ uint16_t wlist[4][kTileThreads + 4];  // per wave: slot byte offset | selector << 14
     __shared__ uint8_t sqm[kTileThreads];        // per staged record: the 8 quadrants it may reach
     __shared__ uint32_t sopen[4];
-#if GS_STRIP_PAD  // A/B knob: LDS padding (bytes) that caps the workgroups per CU
-    __shared__ uint32_t lds_pad[GS_STRIP_PAD / 4];
-    if (a.width < 0) lds_pad[blockIdx.x % (GS_STRIP_PAD / 4)] = 0;  // (never: keeps the array)
-#endif
 
     // XCD-aware remap (as composite_kernel): blocks b and b + 8 share an XCD,
     // so a bin's two halves (consecutive wg) run on one XCD and share its list
@@ -531,7 +515,7 @@ __global__ __launch_bounds__(256, GS_STRIP_WAVES) __attribute__((amdgpu_num_sgpr
     const uint32_t per_row = 2u * (uint32_t)a.tiles_x;
     int owned_row, bx, by;
     const uint32_t half = wg & 1u;  // the bin's top (0) or bottom (1) row of tiles
-    if (GS_COMPOSITE_LPT && a.order && !a.rows) {  // (single-GPU frames: every row owned)
+    if (a.order && !a.rows) {  // (single-GPU frames: every row owned)
         const uint32_t ob = a.order[wg >> 1];
         owned_row = by = (int)(ob / (uint32_t)a.tiles_x);
         bx = (int)(ob - (uint32_t)by * (uint32_t)a.tiles_x);
@@ -657,8 +641,7 @@ __global__ __launch_bounds__(256, GS_STRIP_WAVES) __attribute__((amdgpu_num_sgpr
     uint32_t wendA = 0u, wendB = 0u;  // (PASS 1) end of the last batch each quadrant walked with an open pixel
     const uint32_t* const wl2 = reinterpret_cast<const uint32_t*>(wlist[wave]);
     for (uint32_t b = rg.x; b < rg.y; b += kTileThreads) {
-#if GS_STRIP_PRIO
-        // (A/B) progress-ordered issue priority: a workgroup's waves drop
+        // progress-ordered issue priority: a workgroup's waves drop
         // priority as they walk batches, so late-started workgroups are not
         // starved behind older ones (age arbitration) into a long drain
         {
@@ -668,7 +651,6 @@ __global__ __launch_bounds__(256, GS_STRIP_WAVES) __attribute__((amdgpu_num_sgpr
             else if (nb == 4) __builtin_amdgcn_s_setprio(GS_STRIP_PRIO_TOP > 2 ? GS_STRIP_PRIO_TOP - 2 : 0);
             else if (nb == 6) __builtin_amdgcn_s_setprio(0);
         }
-#endif
         if (b != rg.x) {  // early out (one LDS barrier, as composite_kernel)
             const bool open = __ballot(!fin(TA) || !fin(TB)) != 0;
             if (lane == 0) sopen[wave] = open ? 1u : 0u;
@@ -764,7 +746,6 @@ __global__ __launch_bounds__(256, GS_STRIP_WAVES) __attribute__((amdgpu_num_sgpr
             if (nl == 0u) return;
             auto ld4 = [&](uint32_t o) { return *reinterpret_cast<const float4*>(base + o); };
             auto ld2 = [&](uint32_t o) { return *reinterpret_cast<const float2*>(base + o); };
-#if GS_STRIP_PIPE
             // Rolling read-ahead, one record deep: while record i is
             // composited, record i + 1's reads are in flight (two register
             // sets, A and B, alternate), so every LDS read has a record's
@@ -787,21 +768,6 @@ __global__ __launch_bounds__(256, GS_STRIP_WAVES) __attribute__((amdgpu_num_sgpr
                 cA = ld2(o + kC);
                 body(aB, bB, cB, e >> 30);
             }
-#else
-            uint32_t w2 = wl2[0];
-            for (uint32_t i = 0; i < nl; i += 2) {
-                if (__ballot(!fin(TA) || !fin(TB)) == 0) break;
-                const uint32_t e = __builtin_amdgcn_readfirstlane(w2);
-                const uint32_t o0 = w2 & 0x3FFFu, o1 = (w2 >> 16) & 0x3FFFu;
-                const float4 a0 = ld4(o0), b0 = ld4(o0 + 16u);
-                const float2 c0 = ld2(o0 + kC);
-                const float4 a1 = ld4(o1), b1 = ld4(o1 + 16u);
-                const float2 c1 = ld2(o1 + kC);
-                if (i + 2 < nl) w2 = wl2[(i >> 1) + 1];
-                body(a0, b0, c0, (e >> 14) & 3u);
-                body(a1, b1, c1, e >> 30);
-            }
-#endif
         };
         if (wt) walk(std::integral_constant<uint32_t, 1>{});
         else walk(std::integral_constant<uint32_t, 0>{});
@@ -858,11 +824,7 @@ __global__ __launch_bounds__(256, GS_STRIP_WAVES) __attribute__((amdgpu_num_sgpr
     }
 }
 
-#ifndef GS_COMPOSITE_STRIP  // A/B knob: 0 = the tile/live50 frames on composite_kernel
-#define GS_COMPOSITE_STRIP 1
-#endif
-
-bool composite_strip(uint32_t bins) { return GS_COMPOSITE_STRIP && bins > kStripMinBins; }
+bool composite_strip(uint32_t bins) { return bins > kStripMinBins; }
 
 template <int MODE, bool CAP, int SLAB = 0, int PASS = 0>
 static hipError_t launch_mode(const CompositeArgs& a, hipStream_t st, hipEvent_t t0 = nullptr,

@@ -73,8 +73,7 @@ constexpr int kScanItems = 4096;  // per block
 hipError_t launch_tile_count_totals(const uint32_t* rect_lo, const uint32_t* rect_hi, uint32_t n, RowOwnership own,
                                     bool masked, uint64_t* partials, uint64_t* total, uint32_t* seg_sample,
                                     uint2* ranges, uint32_t nranges, uint32_t* npairs, uint64_t cap,
-                                    uint32_t* zero, uint32_t nzero, hipStream_t st, hipEvent_t done = nullptr,
-                                    unsigned long long seq = 0);
+                                    uint32_t* zero, uint32_t nzero, hipStream_t st, hipEvent_t done = nullptr);
 // (done: recorded by the totals kernel's own dispatch packet, not a separate
 // marker packet, which would leave a ~6 us bubble in the stream.)
 // The scan half alone, after a preprocess with PreFuse: the block sums in
@@ -94,8 +93,7 @@ hipError_t launch_tile_count_totals(const uint32_t* rect_lo, const uint32_t* rec
 // seg_sample null too: total[2..3] = 0, no sample).
 hipError_t launch_scan_partials_fused(unsigned long long* part, uint32_t nb, uint64_t* partials, uint64_t* total,
                                       uint32_t* seg_sample, uint32_t* npairs, uint64_t cap, hipStream_t st,
-                                      hipEvent_t done = nullptr, unsigned long long seq = 0, bool front = false,
-                                      bool lookback = false);
+                                      hipEvent_t done = nullptr, bool front = false, bool lookback = false);
 // Front-only emission of a depth-cut frame (index order, every
 // bin row owned): per 4096-splat block, the pairs the front duplicate emits
 // (launch_scan_duplicate front): a splat whose rect lies within 4x4 bins
@@ -115,9 +113,6 @@ hipError_t launch_fallback_pairs(const uint32_t* rect_lo, const uint32_t* rect_h
                                  bool masked, uint32_t tiles_x, int bin_bits, const uint32_t* table, uint32_t nbins,
                                  const unsigned long long* open, uint64_t* part, uint64_t* total, uint32_t* npairs,
                                  uint32_t* kept, uint64_t cap, uint32_t* keys, uint32_t* vals, hipStream_t st);
-// (seq > 0: after total[0..4] the totals kernel stores seq into total[5] with
-// a system-scope release, for a host that polls host-mapped `total` instead
-// of waiting for `done`.)
 // The first LSD pass's digit counts of the pairs, C[digit][tile] with
 // `ntiles` columns, tiles of `tile` pairs, digit = bin & mask: the index-order
 // duplicate adds them up as it writes (C zeroed before), so the sort skips
@@ -178,14 +173,11 @@ hipError_t launch_scan_duplicate(const uint32_t* order, const uint32_t* rect_lo,
 #define GS_SEG_IPT 16
 #endif
 constexpr uint32_t kSegLdsMax = GS_SEG_NT * GS_SEG_IPT;  // lists sorted inside one workgroup (bin_depth_sort.hip)
-#ifndef GS_SEG_CLASSES  // 1: frames of >= GS_SEG_CLASS_MIN_BINS bins sort short lists (<= kSegSmallMax) in a launch of narrower workgroups
-#define GS_SEG_CLASSES 1
-#endif
+// Frames of >= GS_SEG_CLASS_MIN_BINS bins sort short lists (<= kSegSmallMax) in
+// a launch of narrower workgroups; frames of fewer bins whose lists are front
+// lists (short_lists) sort in 256-lane workgroups.
 #ifndef GS_SEG_CLASS_MIN_BINS
 #define GS_SEG_CLASS_MIN_BINS 4096
-#endif
-#ifndef GS_SEG_SHORT  // A/B knob: 1 = frames of fewer bins whose lists are front lists (short_lists) sort in 256-lane workgroups
-#define GS_SEG_SHORT 1
 #endif
 #ifndef GS_SEG_SMALL_NT
 #define GS_SEG_SMALL_NT 256

@@ -15,33 +15,18 @@
 
 namespace gs {
 
-#ifndef GS_PRE_NT  // A/B knob: scene loads with the non-temporal hint (read once per frame)
-#define GS_PRE_NT 1
-#endif
 typedef float gs_f4 __attribute__((ext_vector_type(4)));
 typedef float gs_f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float4 scene_load(const float4* p) {
-#if GS_PRE_NT
     const gs_f4 v = __builtin_nontemporal_load(reinterpret_cast<const gs_f4*>(p));
     return make_float4(v.x, v.y, v.z, v.w);
-#else
-    return *p;
-#endif
 }
 __device__ __forceinline__ float2 scene_load(const float2* p) {
-#if GS_PRE_NT
     const gs_f2 v = __builtin_nontemporal_load(reinterpret_cast<const gs_f2*>(p));
     return make_float2(v.x, v.y);
-#else
-    return *p;
-#endif
 }
 __device__ __forceinline__ float scene_load(const float* p) {
-#if GS_PRE_NT
     return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
 }
 
 // A splat's SH rest coefficients, k-major with r,g,b interleaved: flat j =
@@ -121,24 +106,7 @@ __device__ __forceinline__ void sh_color(const ShCoef<DEG>& coef, float px, floa
     }
 }
 
-
-#ifndef GS_PRE_EARLY  // A/B knob: 1 = rotation, scale (and the SH0 colour) loaded with the position
-#define GS_PRE_EARLY 0     // (one dependent round trip fewer, bytes for culled splats too)
-#endif
-
-#ifndef GS_PRE_PRIO  // A/B knob: issue priority (0..3) of the projection's waves
-#define GS_PRE_PRIO 0
-#endif
-
-#ifndef GS_PRE_FULLREC  // A/B knob: 1 = culled splats of a full frame write a zero record (whole-line record stores)
-#define GS_PRE_FULLREC 1
-#endif
-
-#ifndef GS_PRE_BAND_CULL  // A/B knob: 1 = band frames cull splats off the band before their covariance
-#define GS_PRE_BAND_CULL 1
-#endif
-
-#ifndef GS_PRE_WAVES  // A/B knob: min waves per SIMD (caps the VGPRs)
+#ifndef GS_PRE_WAVES  // tunable: min waves per SIMD (caps the VGPRs)
 #define GS_PRE_WAVES 8
 #endif
 
@@ -179,11 +147,6 @@ __global__ __launch_bounds__(256, (EPI == 2 && DEG == 3) ? 7 : GS_PRE_WAVES) voi
                                                          unsigned long long* __restrict__ zero8,
                                                          const PreFuse fuse, const ShardFuse shard) {
     uint32_t i = blockIdx.x * 256u + threadIdx.x;
-#if GS_PRE_PRIO
-    // (A/B) the projection bounds the pipelined frame (projection + chain):
-    // its waves ahead of the co-running composite's in issue arbitration
-    __builtin_amdgcn_s_setprio(GS_PRE_PRIO);
-#endif
     if (i < 2 && zero8) zero8[i] = 0ull;
     if constexpr (EPI == 0)
         if (i >= s.n) return;
@@ -194,25 +157,12 @@ __global__ __launch_bounds__(256, (EPI == 2 && DEG == 3) ? 7 : GS_PRE_WAVES) voi
     const float* VP = U.VP;
 
     float4 a0 = scene_load(&s.p0[i]);
-#if GS_PRE_EARLY
-    float4 q_e = scene_load(&s.p1[i]);
-    float4 a2_e = scene_load(&s.p2[i]);
-    [[maybe_unused]] float2 a3_e;
-    if constexpr (DEG == 0) a3_e = scene_load(&s.p3[i]);
-#endif
     float px = a0.x, py = a0.y, pz = a0.z;
     // K3: view position, zFront (tile.metal:94-105)
     float vx = xform_row(V, 0, px, py, pz);
     float vy = xform_row(V, 1, px, py, pz);
     float vz = xform_row(V, 2, px, py, pz);
     float zf = -vz;
-#if GS_PRE_EARLY
-    // (an empty asm consuming the early loads: the compiler otherwise sinks
-    // them back into the branch that uses them)
-    asm volatile("" : "+v"(q_e.x), "+v"(q_e.y), "+v"(q_e.z), "+v"(q_e.w), "+v"(a2_e.x), "+v"(a2_e.y), "+v"(a2_e.z),
-                 "+v"(a2_e.w));
-    if constexpr (DEG == 0) asm volatile("" : "+v"(a3_e.x), "+v"(a3_e.y));
-#endif
     if (zf >= 1e-4f) {
         // K6 z-clip on NDC z in [0,1] (tile.metal:145-152)
         float clx = xform_row(VP, 0, px, py, pz);
@@ -222,15 +172,11 @@ __global__ __launch_bounds__(256, (EPI == 2 && DEG == 3) ? 7 : GS_PRE_WAVES) voi
         float invw = 1.0f / clw;
         float ndcz = clz * invw;
         if (ndcz >= 0.0f && ndcz <= 1.0f && zf >= 0.001f) {
-#if GS_PRE_EARLY
-            const float4 q = q_e, a2 = a2_e;
-#else
             float4 a2 = scene_load(&s.p2[i]);
             // (BAND: a splat whose rect provably misses the band's rows is
             // culled before its rotation is read and its covariance formed)
             if (!BAND || !band_culled(U, V, vx, vy, zf, cly * invw, a2)) {
             float4 q = scene_load(&s.p1[i]);
-#endif
             // K1 (tile.metal:40-49)
             float qs = q.x * q.x;
             qs = __builtin_fmaf(q.y, q.y, qs);
@@ -331,13 +277,7 @@ __global__ __launch_bounds__(256, (EPI == 2 && DEG == 3) ? 7 : GS_PRE_WAVES) voi
                     // (colour inputs loaded only for splats on screen; loading
                     // them with the shape, a round trip earlier, was measured
                     // slower: 0.30-0.33 vs 0.29 ms, 45 more live registers)
-#if GS_PRE_EARLY
-                    float2 a3;
-                    if constexpr (DEG == 0) a3 = a3_e;
-                    else a3 = scene_load(&s.p3[i]);
-#else
                     const float2 a3 = scene_load(&s.p3[i]);
-#endif
                     ShCoef<DEG> coef;
                     if constexpr (DEG > 0) sh_load<DEG>(s, i, coef);
                     sh_color<DEG>(coef, px, py, pz, U.campos, a2.w, a3.x, a3.y, cr, cg, cbl);
@@ -346,9 +286,6 @@ __global__ __launch_bounds__(256, (EPI == 2 && DEG == 3) ? 7 : GS_PRE_WAVES) voi
                     const float4 rb = make_float4(e2x * k2, e2y * k2, a0.w, cr);
                     // 8x8 cells of the rect the ellipse provably misses (the
                     // composite skips them; frames up to kCellMaskDim px)
-#ifdef GS_AB_NO_MASKS  // A/B build: masks off (cost of the masks in this kernel)
-                    const uint32_t excl = 0u, bexcl = 0u;
-#else
                     uint32_t excl = 0u, bexcl = 0u;
                     if (U.cell_mask) {
                         // a rect within 4x4 cells: its cell mask, and the bin
@@ -357,7 +294,6 @@ __global__ __launch_bounds__(256, (EPI == 2 && DEG == 3) ? 7 : GS_PRE_WAVES) voi
                         excl = rm.cell;
                         bexcl = rm.bin;
                     }
-#endif
                     o[0] = ra;
                     o[1] = rb;
                     if constexpr (kRecFloat4 == 4) o[3] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // (whole 64-B slot)
@@ -370,12 +306,9 @@ __global__ __launch_bounds__(256, (EPI == 2 && DEG == 3) ? 7 : GS_PRE_WAVES) voi
                     rhi = rect_with_mask(x1 | (y1 << 16), (bexcl >> 8) & 0xFu, bexcl >> 12);
                 }
             }
-#if !GS_PRE_EARLY
             }  // (the band cull)
-#endif
         }
     }
-#if GS_PRE_FULLREC
     // a culled splat writes a zero record too, so a wave's record stores
     // cover whole lines instead of leaving holes (partially written lines);
     // no list ever holds a culled splat, so its record is never read.  Not in
@@ -386,7 +319,6 @@ __global__ __launch_bounds__(256, (EPI == 2 && DEG == 3) ? 7 : GS_PRE_WAVES) voi
 #pragma unroll
         for (int k = 0; k < kRecFloat4; ++k) o[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
-#endif
     dkey[i] = key;
     rect_lo[i] = rlo;
     rect_hi[i] = rhi;
@@ -470,8 +402,8 @@ hipError_t launch_preprocess(const SceneDev& s, int sh_degree, const FrameUnifor
         return hipErrorInvalidValue;
     const int epi = fuse.part ? 1 : shard.owner ? 2 : 0;
     // (band frames: the band cull, its own instances, so the full frame's
-    // kernels keep their code; not with GS_PRE_EARLY, which loads before it)
-    const bool band = GS_PRE_BAND_CULL && !GS_PRE_EARLY && epi != 2 && (U.band_y0 > 0 || U.band_y1 < U.height - 1);
+    // kernels keep their code)
+    const bool band = epi != 2 && (U.band_y0 > 0 || U.band_y1 < U.height - 1);
     switch (sh_degree * 3 + epi) {
 #define GS_PRE_CASE(D, E)                                                                                          \
     case D * 3 + E:                                                                                                \

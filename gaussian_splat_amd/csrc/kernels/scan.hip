@@ -20,9 +20,6 @@
 namespace gs {
 
 constexpr int kScanIpt = kScanItems / 256;  // 16 consecutive items per lane
-#ifndef GS_BUF_LOADS  // A/B knob: 1 = the count and duplicate kernels read through raw buffer resources (BufU32)
-#define GS_BUF_LOADS 0
-#endif
 
 struct CountSrc {
     const uint32_t* lo;
@@ -326,16 +323,7 @@ __global__ __launch_bounds__(1024) void filtered_count_kernel(const uint32_t* __
     const uint32_t tid = threadIdx.x, nblocks = (n + kScanItems - 1) / kScanItems;
     uint32_t lo[IPT], hi[IPT], dk[IPT];
     auto load = [&](uint32_t b, uint32_t* l, uint32_t* h, uint32_t* d) {
-#if GS_BUF_LOADS  // (A/B: raw buffer loads, reads past n return 0)
-        const uint32_t base = b < nblocks ? b * kScanItems : n;
-        const BufU32 blo(rect_lo, base, n, kScanItems), bhi(rect_hi, base, n, kScanItems), bdk(dkey, base, n, kScanItems);
-#pragma unroll
-        for (int k = 0; k < IPT; ++k) {
-            l[k] = blo[k * 1024 + tid];
-            h[k] = bhi[k * 1024 + tid];
-            d[k] = bdk[k * 1024 + tid];
-        }
-#else  // (clamped: none waits in a branch; past n counted as nothing below)
+        // (clamped: none waits in a branch; past n counted as nothing below)
 #pragma unroll
         for (int k = 0; k < IPT; ++k) {
             const uint32_t j = min(b * kScanItems + k * 1024 + tid, n - 1u);
@@ -343,7 +331,6 @@ __global__ __launch_bounds__(1024) void filtered_count_kernel(const uint32_t* __
             h[k] = rect_hi[j];
             d[k] = dkey[j];
         }
-#endif
     };
     uint32_t b = blockIdx.x;
     load(b, lo, hi, dk);
@@ -392,39 +379,24 @@ __global__ __launch_bounds__(1024) void filtered_count_kernel(const uint32_t* __
 // emit_bin_pairs writes there.  c: the item's pair count (0: none), start:
 // its first pair - off0.  on_pair(g, bin, key) runs for every pair written
 // (g absolute) and returns the key stored.
-// gen: the wave's chunk counter (GS_DUP_TAG: a mark carries its chunk's
-// number, so stale marks are ignored instead of cleared; mk starts at ~0).
-#ifndef GS_DUP_TAG  // A/B knob
-#define GS_DUP_TAG 0
-#endif
 // inc: the item's emitted bins of a rect within 4x4 bins (bit dy*4 + dx; the
 // included ones with excluded bins, or the kept ones of a filtered emission),
 // or 0: every bin of the rect in row-major order (minus none).
 template <typename F>
 __device__ __forceinline__ void coop_emit(uint32_t* mk, uint32_t lane, const BinRect& r, uint32_t inc, uint32_t c,
                                           uint32_t start, uint32_t off0, uint32_t val, uint32_t khi, uint32_t tiles_x,
-                                          uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t& gen,
-                                          F&& on_pair) {
+                                          uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, F&& on_pair) {
     const uint32_t T = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_dpp<true>(c > 0u ? start + c : 0u), 63);
     const uint32_t cols = r.bx1 - r.bx0 + 1u;
     const uint32_t pa = r.bx0 | (r.by0 << 16), pb = (cols & 0xFFFFu) | (inc << 16);
     uint32_t carry = 0;
     for (uint32_t q0 = 0; q0 < T; q0 += 64u) {
-#if GS_DUP_TAG
-        ++gen;
-        wave_lds_sync();  // the last chunk's mark reads are done
-        if (c > 0u && start >= q0 && start - q0 < 64u) mk[start - q0] = gen << 7 | (lane + 1u);
-        wave_lds_sync();
-        const uint32_t mv = mk[lane];
-        uint32_t own1 = wave_scan_dpp<true>(mv >> 7 == gen ? mv & 127u : 0u);
-#else
         wave_lds_sync();  // the last chunk's mark reads are done
         mk[lane] = 0u;
         wave_lds_sync();
         if (c > 0u && start >= q0 && start - q0 < 64u) mk[start - q0] = lane + 1u;
         wave_lds_sync();
         uint32_t own1 = wave_scan_dpp<true>(mk[lane]);
-#endif
         own1 = own1 > carry ? own1 : carry;
         carry = (uint32_t)__builtin_amdgcn_readlane((int)own1, 63);
         const int ol = (int)(own1 > 0u ? own1 - 1u : 0u);
@@ -464,9 +436,6 @@ __device__ __forceinline__ uint32_t pad32(uint32_t i) { return i + (i >> 5); }  
 #define GS_DUP_THREADS 1024
 #endif
 constexpr int kDupThreads = GS_DUP_THREADS;          // 16 waves: many waves to hide the pair stores
-#ifndef GS_DUP_COOP  // A/B knob: 1 = wave-cooperative emission when every bin row is owned
-#define GS_DUP_COOP 1
-#endif
 constexpr int kDupIpt = kScanItems / kDupThreads;    // 4 items per lane
 
 // Exclusive scan over a kDupThreads-lane workgroup (LDS-only barriers).
@@ -488,7 +457,7 @@ __device__ __forceinline__ uint32_t block_dup_exclusive_scan(uint32_t v, uint32_
     return base + inc - v;
 }
 
-// Decoupled look-back (the front duplicate, GS_DUP_LOOKBACK): block b's
+// Decoupled look-back (the front duplicate): block b's
 // status word lb[b] is 0 (not yet), kLbAgg | its pair count, or kLbIncl | the
 // pairs of blocks 0..b.  Called by wave 0 with the block's count; returns the
 // pairs of blocks 0..b-1 in every lane.  Each step reads the 64 statuses below
@@ -577,18 +546,6 @@ __global__ __launch_bounds__(kDupThreads) void scan_duplicate_kernel(CountSrc sr
     // value would be waited for at once)
     uint64_t part = LB ? 0ull : partials[bid];
     uint32_t rlo[kDupIpt], rhi[kDupIpt], dk[kDupIpt], ord[kDupIpt];
-#if GS_BUF_LOADS  // (A/B: raw buffer loads, reads past n return 0; those items get the empty rect below)
-    const BufU32 blo(src.lo, blk, n, kScanItems), bhi(src.hi, blk, n, kScanItems),
-        bdk(dkey ? dkey : src.lo, blk, n, kScanItems), bord(order ? order : src.lo, blk, n, kScanItems);
-#pragma unroll
-    for (int k = 0; k < kDupIpt; ++k) {
-        const uint32_t i = k * kDupThreads + tid;
-        rlo[k] = blo[i];
-        rhi[k] = bhi[i];
-        dk[k] = bdk[i];
-        ord[k] = bord[i];
-    }
-#else
     const uint32_t* dsrc = dkey ? dkey : src.lo;
     const uint32_t* osrc = order ? order : src.lo;
 #pragma unroll
@@ -599,7 +556,6 @@ __global__ __launch_bounds__(kDupThreads) void scan_duplicate_kernel(CountSrc sr
         dk[k] = dsrc[j];
         ord[k] = osrc[j];
     }
-#endif
     if (FM != kDupPlain) stage_tab16(fcut, nbins, scut);  // (a depth key is < 2^15: min(t, 0xFFFF) keeps every comparison)
     if (pc.C)
         for (uint32_t i = tid; i < kDupCountTiles * kSortBins; i += kDupThreads) (&lh[0][0])[i] = 0u;
@@ -682,15 +638,14 @@ __global__ __launch_bounds__(kDupThreads) void scan_duplicate_kernel(CountSrc sr
         else atomicAdd(&pc.C[(size_t)d * pc.ntiles + t], 1u);
         return key;
     };
-    if (FM != kDupBehind && GS_DUP_COOP && !src.own.owner) {
+    if (FM != kDupBehind && !src.own.owner) {
         // wave-cooperative emission (every bin row owned): each wave's 64
         // consecutive items of a round own one contiguous pair run, written
         // 64 pairs per step by all lanes, so a large splat does not hold its
         // wave's other lanes idle (coop_emit; the same pairs at the same
         // offsets as the per-lane loop below)
         const uint32_t lane = tid & 63u, wave = tid >> 6;
-        uint32_t gen = 0;
-        mk[wave][lane] = ~0u;  // (no chunk's tag)
+        mk[wave][lane] = ~0u;  // (coop_emit clears its marks before every chunk)
 #pragma unroll
         for (int k = 0; k < kDupIpt; ++k) {
             const uint32_t i = k * kDupThreads + tid, j = blk + i;
@@ -707,11 +662,11 @@ __global__ __launch_bounds__(kDupThreads) void scan_duplicate_kernel(CountSrc sr
             const uint32_t off0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);
             const uint32_t khi = dkey ? dk[k] << bin_bits : 0u;
             const uint32_t val = order ? ord[k] : j;
-            if (pc.C) coop_emit(mk[wave], lane, r, inc, c, off - off0, off0, val, khi, tiles_x, keys, vals, gen, count);
+            if (pc.C) coop_emit(mk[wave], lane, r, inc, c, off - off0, off0, val, khi, tiles_x, keys, vals, count);
             else if (FM == kDupMark || FM == kDupFront)
-                coop_emit(mk[wave], lane, r, inc, c, off - off0, off0, val, khi, tiles_x, keys, vals, gen,
+                coop_emit(mk[wave], lane, r, inc, c, off - off0, off0, val, khi, tiles_x, keys, vals,
                           [&](uint32_t, uint32_t bin, uint32_t key) { return mark(bin, key); });
-            else coop_emit(mk[wave], lane, r, inc, c, off - off0, off0, val, khi, tiles_x, keys, vals, gen,
+            else coop_emit(mk[wave], lane, r, inc, c, off - off0, off0, val, khi, tiles_x, keys, vals,
                            [](uint32_t, uint32_t, uint32_t key) { return key; });
         }
     } else
@@ -847,17 +802,15 @@ __global__ __launch_bounds__(256) void duplicate_coop_kernel(CountSrc src, uint3
     const BinRect r = bin_rect(lo, hi, src.masked);
     const uint32_t c = rect_tile_count(lo, hi, src.own, src.masked);
     const uint32_t off0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);  // lane 0 is valid
-    uint32_t gen = 0;
-    mk[wave][lane] = ~0u;  // (no chunk's tag)
-    coop_emit(mk[wave], lane, r, r.excl ? rect_inc16(r) : 0u, c, off - off0, off0, val, khi, tiles_x, keys, vals, gen,
+    mk[wave][lane] = ~0u;  // (coop_emit clears its marks before every chunk)
+    coop_emit(mk[wave], lane, r, r.excl ? rect_inc16(r) : 0u, c, off - off0, off0, val, khi, tiles_x, keys, vals,
               [](uint32_t, uint32_t, uint32_t key) { return key; });
 }
 
 hipError_t launch_tile_count_totals(const uint32_t* rect_lo, const uint32_t* rect_hi, uint32_t n, RowOwnership own,
                                     bool masked, uint64_t* partials, uint64_t* total, uint32_t* seg_sample,
                                     uint2* ranges, uint32_t nranges, uint32_t* npairs, uint64_t cap,
-                                    uint32_t* zero, uint32_t nzero, hipStream_t st, hipEvent_t done,
-                                    unsigned long long seq) {
+                                    uint32_t* zero, uint32_t nzero, hipStream_t st, hipEvent_t done) {
     const CountSrc src{rect_lo, rect_hi, own, masked};
     const uint32_t nb = (n + kScanItems - 1) / kScanItems;
     if (nb == 0) {
@@ -873,16 +826,16 @@ hipError_t launch_tile_count_totals(const uint32_t* rect_lo, const uint32_t* rec
         scan_reduce_kernel<<<nb, 256, 0, st>>>(src, n, partials, ranges, nranges, zero, nzero);
     }
     hipExtLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(kPartThreads), 0, st, nullptr, done, 0, partials, nb,
-                          total, seg_sample, npairs, cap, nullptr, seq, 0u, nullptr, nullptr);
+                          total, seg_sample, npairs, cap, nullptr, 0ull, 0u, nullptr, nullptr);
     return hipGetLastError();
 }
 
 hipError_t launch_scan_partials_fused(unsigned long long* part, uint32_t nb, uint64_t* partials, uint64_t* total,
                                       uint32_t* seg_sample, uint32_t* npairs, uint64_t cap, hipStream_t st,
-                                      hipEvent_t done, unsigned long long seq, bool front, bool lookback) {
+                                      hipEvent_t done, bool front, bool lookback) {
     if (!part) return hipErrorInvalidValue;
     hipExtLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(kPartThreads), 0, st, nullptr, done, 0, partials, nb,
-                          total, seg_sample, npairs, cap, part, seq, lookback ? kPartLookback : front ? 3u : 0u,
+                          total, seg_sample, npairs, cap, part, 0ull, lookback ? kPartLookback : front ? 3u : 0u,
                           nullptr, nullptr);
     return hipGetLastError();
 }
@@ -935,17 +888,15 @@ hipError_t launch_scan_duplicate(const uint32_t* order, const uint32_t* rect_lo,
     // (the marks: index order, the cooperative emission, the flag above the depth key)
     if (np_out && (order || own.owner)) return hipErrorInvalidValue;  // (look-back: index order, every row owned)
     if ((fcut || front) &&
-        (!fcut || order || own.owner || !GS_DUP_COOP || !dkey || nbins > kDupCutBins || bin_bits + kDepthBits > 31))
+        (!fcut || order || own.owner || !dkey || nbins > kDupCutBins || bin_bits + kDepthBits > 31))
         return hipErrorInvalidValue;
     if (order) {  // depth order: per-item offsets, then one splat per lane
         if (!offsets) return hipErrorInvalidValue;
         scan_down_kernel<<<nb, 256, 0, st>>>(src, n, partials, offsets);
-#ifndef GS_AB_DUP_LANE
         if (!own.owner)
             duplicate_coop_kernel<<<(n + 255) / 256, 256, 0, st>>>(src, n, order, offsets, tiles_x, keys, vals, npairs,
                                                                    dkey, bin_bits);
         else
-#endif
             duplicate_kernel<<<(n + 255) / 256, 256, 0, st>>>(src, n, order, offsets, tiles_x, keys, vals, npairs, dkey,
                                                               bin_bits);
         return hipGetLastError();

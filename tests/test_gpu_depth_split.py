@@ -367,3 +367,70 @@ def test_front_only_retry_after_zoom_out(built, fif, scale):
     assert sum(fronts[1:5]) >= 3, fronts                      # the still frames emitted their front pairs only
     grew = [k for k in range(1, len(pairs)) if pairs[k] > 1.2 * pairs[k - 1]]
     assert grew and any(fronts[k] for k in grew), (pairs, fronts)  # a front-only frame outgrew the buffers
+
+
+def _alloc_granule(device=0):
+    """The minimum device allocation granularity the HIP runtime reports, in bytes."""
+    import ctypes as C
+
+    class Prop(C.Structure):  # hipMemAllocationProp
+        _fields_ = [("type", C.c_int), ("handle_type", C.c_int), ("loc_type", C.c_int), ("loc_id", C.c_int),
+                    ("win32_meta", C.c_void_p), ("alloc_flags", C.c_ubyte * 4)]
+
+    with open("/proc/self/maps") as f:  # (the runtime torch loaded)
+        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
+    prop, g = Prop(type=1, loc_type=1, loc_id=device), C.c_size_t(0)  # pinned device memory on `device`
+    err = C.CDLL(path).hipMemGetAllocationGranularity(C.byref(g), C.byref(prop), 0)  # 0: the minimum
+    assert err == 0 and g.value > 0, (err, g.value)
+    return int(g.value)
+
+
+# Largest deviation of the free memory after cycles 2-6 from cycle 1, measured
+# on an MI355X with the hand-written release list this test was written
+# against: every one of cycles 2-6 left 8,388,608 bytes (8 MiB) less free
+# than cycle 1, the same each time (a runtime pool that stays); the runtime
+# reports a granule of 4096 bytes.  Allowed: twice that, 16,777,216 bytes.
+_HANDLE_FREE_MEASURED = 8 << 20
+
+
+def test_destroying_a_handle_returns_its_device_memory(built):
+    """gs_destroy frees every device buffer of the handle: the buffers are
+    DevBuf members, freed by their destructors, both buffer sets included.
+    Six create / initialize / render / close cycles with depth cuts and two
+    frames in flight (both sets, the cut tables, the front lists): the free
+    device memory after cycles 2-6 equals that after cycle 1, which absorbs
+    the runtime's one-time allocations, within twice the deviation measured
+    before the buffers freed themselves (_HANDLE_FREE_MEASURED) and at least
+    one allocation granule.  The frames go into one preallocated tensor, so
+    torch's allocator takes no part.  A buffer that leaks does so in every
+    cycle, so after cycle 6 it shows five times: anything above a fifth of
+    the allowance (3.4 MB) fails, and the scene is sized so that rec
+    (200,000 x 48 B = 9.6 MB) and each pair buffer (1.2M pairs x 4 B =
+    4.9 MB) exceed that.  Smaller
+    buffers (counters, totals, cut tables at this frame size) are covered by
+    construction, as DevBuf members, not by this test."""
+    import torch
+
+    from gaussian_splat_amd import InstancedSplatRenderer, Options
+    W = H = 256
+    sc = _scene(200000, 3, 0, 1.0, scale=16.0)  # (large splats: enough pairs at 64 bins for the pair buffers to count)
+    views = _path(W, H, "orbit", 4)
+    out = torch.empty((H, W, 4), dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()
+    free = []
+    for _ in range(6):
+        r = InstancedSplatRenderer(sc, Options(crop=False, depth_split=True, frames_in_flight=2))
+        r.initialize(0)
+        for V, P in views:
+            r.render(V, P, W, H, out=out)
+        torch.cuda.synchronize()
+        st = r.last_stats()
+        assert st["cut_frame"] == 1
+        r.close()
+        free.append(torch.cuda.mem_get_info(0)[0])
+    granule = _alloc_granule(0)
+    allow = max(2 * _HANDLE_FREE_MEASURED, granule)
+    dev = [f - free[0] for f in free[1:]]
+    print(f"free after cycle 1: {free[0]}, deviations of cycles 2-6: {dev}, granule {granule}, allowance {allow}, "
+          f"pairs {st['pairs']}")
+    assert max(abs(d) for d in dev) <= allow, (dev, allow)

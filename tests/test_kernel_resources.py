@@ -111,7 +111,7 @@ def test_composite_budget(comp_res, pass_):
 
 def test_bin_depth_sort_budget(seg_res):
     # the per-bin sort: one 512-lane launch (lists up to 8192 pairs in LDS), and the 256-lane
-    # short class of frames of many bins (GS_SEG_CLASSES): no spill, six waves per SIMD
+    # short class of frames of many bins (two size classes, launch_bin_depth_sort): no spill, six waves per SIMD
     for pat in (r"bin_depth_sort_kernelILi512ELi16ELi6ELi0EE", r"bin_depth_sort_kernelILi256ELi16ELi6ELi1EE"):
         r = _one(seg_res, pat)
         assert r["ScratchSize"] == 0 and r["Occupancy"] >= 6, (pat, r)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Build a libgsplat.so variant into ab/<name>.so with extra compiler flags
-(A/B timing with tools/ab.sh, or debug builds such as -DGS_COMPOSITE_COUNTERS).
+(A/B timing of a numeric tunable with tools/ab.sh, e.g. -DGS_SEG_NT=256, or
+instrumented builds such as -DGS_COMPOSITE_TRACE).
 
   python tools/build_variant.py NAME [FLAG ...]
 """
