@@ -279,6 +279,38 @@ class InstancedSplatRenderer:
                               1, C.c_void_p(stream)), "gs_render")
         return out
 
+    def render_depth(self, view, proj, width: int, height: int, out=None, depth=None, stream=None):
+        """Render colour and depth in one composite pass (gs_render_depth): returns
+        (rgba, depth), torch float32 CUDA tensors (H, W, 4) and (H, W).  `rgba` is
+        render()'s frame bit for bit; `depth` is the accumulated view depth D
+        (each splat's zF composited as a colour channel, 0 where nothing lands):
+        in tile mode the expected depth is depth / rgba[..., 3] where alpha > 0.
+        Tile and live50 modes without a fragment cap."""
+        import torch
+
+        dev = f"cuda:{self.device or 0}"
+        if out is None:
+            out = torch.empty((height, width, 4), dtype=torch.float32, device=dev)
+        if depth is None:
+            depth = torch.empty((height, width), dtype=torch.float32, device=dev)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == width * height * 4
+        assert depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous() and depth.numel() == width * height
+        assert depth.device == out.device
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device).cuda_stream
+        check(lib().gs_render_depth(self._h, _mat16(view), _mat16(proj), int(width), int(height),
+                                    C.c_void_p(out.data_ptr()), C.c_void_p(depth.data_ptr()), 1, C.c_void_p(stream)),
+              "gs_render_depth")
+        return out, depth
+
+    def render_depth_host(self, view, proj, width: int, height: int):
+        """render_depth into host memory: (rgba (H, W, 4), depth (H, W)) numpy float32."""
+        out = np.empty((height, width, 4), np.float32)
+        depth = np.empty((height, width), np.float32)
+        check(lib().gs_render_depth(self._h, _mat16(view), _mat16(proj), int(width), int(height), out.ctypes.data,
+                                    depth.ctypes.data, 0, None), "gs_render_depth")
+        return out, depth
+
     def render_bgra8(self, view, proj, width: int, height: int, out=None, stream=None):
         """Render as BGRA8Unorm (the reference's drawable format) into `out`
         (torch uint8 CUDA tensor (H, W, 4), bytes B, G, R, A); returns it."""

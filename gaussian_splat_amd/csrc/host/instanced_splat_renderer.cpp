@@ -40,6 +40,15 @@ void InstancedSplatRenderer::renderBGRA8(void* commandBuffer, void* drawableText
                               (int32_t)viewportHeight, static_cast<uint8_t*>(drawableTexture), 1, commandBuffer);
 }
 
+void InstancedSplatRenderer::renderDepth(void* commandBuffer, void* drawableTexture, void* depthTexture,
+                                         const simd_float4x4& viewMatrix, const simd_float4x4& projectionMatrix,
+                                         float viewportWidth, float viewportHeight) {
+    if (!handle_ || gs_point_count(handle_) == 0 || !drawableTexture || !depthTexture) return;
+    status_ = gs_render_depth(handle_, viewMatrix.data(), projectionMatrix.data(), (int32_t)viewportWidth,
+                              (int32_t)viewportHeight, static_cast<float*>(drawableTexture),
+                              static_cast<float*>(depthTexture), 1, commandBuffer);
+}
+
 int InstancedSplatRenderer::getPointCount() const { return (int)gs_point_count(handle_); }
 
 gs_stats InstancedSplatRenderer::lastStats() const {

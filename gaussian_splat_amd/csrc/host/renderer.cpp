@@ -88,6 +88,7 @@ static_assert(!std::is_copy_constructible_v<DevBuf>);
 struct BufSet {
     DevBuf rec, dkey, keys, vals, tkeys, tvals, ranges, thr, rlo, rhi;
     DevBuf qrec, fkeys, fvals;  // depth cuts: quadrant records, front lists (gs_handle::cutbuf)
+    DevBuf zf;                  // depth frames (gs_render_depth): the splats' fp32 view depths
 };
 
 using gsio::sh_coeffs;
@@ -110,6 +111,13 @@ struct gs_handle {
     DevBuf p0, p1, p2, p3, sh4, sh1;
     // per-frame scratch
     DevBuf offsets, partials, sort_scratch, fb;
+    // Depth frames (gs_render_depth).  depth_out: the device
+    // depth image of the frame being enqueued (null: a colour-only frame),
+    // set and cleared by render_frame; fbd: its staging copy for host output;
+    // dstate: the open quadrants' D beside cstate (depth cuts).
+    float* depth_out = nullptr;
+    bool stats_depth = false;  // the frame in `stats` was a depth frame
+    DevBuf fbd, dstate;
     DevBuf dsk, dso, dsl, dsh, dtk, dto, dtl, dth;  // depth sort: keys, order, rect lo/hi (+ ping-pong)
     DevBuf xmask, xcounts, xtotal;  // multi-GPU exchange
     // depth-slab frames: full-frame ownership; the colour pass
@@ -882,6 +890,7 @@ gs_status setup_cuts(gs_handle* h, const gs::FrameUniforms& U, bool cut_frame, h
     }
     GS_HIP(h->cur.qrec.reserve((size_t)T * gs::kQrecWords * 4));
     GS_HIP(reserve_after(h->cstate, (size_t)U.width * U.height * 16, st));
+    if (h->depth_out) GS_HIP(reserve_after(h->dstate, (size_t)U.width * U.height * 4, st));
     h->cut_in = h->cut_valid[h->set] ? h->cut_table(h->set, 0) : nullptr;
     h->cut_out = h->cut_table(h->set, 1);
     // Dilation (a moving camera): a bin's content moves between the frame that
@@ -1085,6 +1094,9 @@ gs_status bin_sort_composite(gs_handle* h, uint32_t m, const uint32_t* dkey, con
     ca.out_bgra8 = out_bgra8;
     ca.cap = h->opt.cap;
     ca.dkey = dkey;
+    ca.zf = h->depth_out ? h->cur.zf.as<float>() : nullptr;  // (depth frames, render_frame)
+    ca.depth_out = h->depth_out;
+    ca.state_d = h->depth_out ? h->dstate.as<float>() : nullptr;
     const uint32_t* vals = nullptr;
     uint64_t P = 0;
     const bool mlab = h->opt.mode == GS_MODE_MLAB;
@@ -1306,9 +1318,11 @@ void fill_stats(gs_handle* h, uint64_t P, const gs::FrameUniforms& U) {
     s.bytes_ranges = 0;  // ranges come out of the last sort pass
     // upper bound until the fetch counter is read (gs_last_stats): every tile
     // of a bin reads the whole list; the early-out stops that short
-    h->stats_fixed_bytes = 4 * T * 8 + (int64_t)U.width * U.height * 16;
+    // (a depth frame: 4 B of zF per fetched record, and the depth image)
+    h->stats_depth = h->depth_out != nullptr;
+    h->stats_fixed_bytes = 4 * T * 8 + (int64_t)U.width * U.height * (h->stats_depth ? 20 : 16);
     h->stats_set = h->set;
-    s.bytes_composite = h->stats_fixed_bytes + 4 * Pi * (4 + 48);
+    s.bytes_composite = h->stats_fixed_bytes + 4 * Pi * (4 + 48 + (h->stats_depth ? 4 : 0));
     s.records_fetched = -1;
     s.pairs_sorted = Pi;
     s.cut_frame = h->cut_frame ? 1 : 0;
@@ -1564,12 +1578,23 @@ gs_status gs_set_cap(gs_handle* h, int32_t cap) {
 
 // One frame into a caller-owned framebuffer: fp32 RGBA (16 B/pixel) or, with
 // bgra8, packed BGRA8Unorm (4 B/pixel, converted inside the composite).
+// depth_user (gs_render_depth; fp32 RGBA frames): also the accumulated depth
+// image, W * H floats, from the same composite pass.
 static gs_status render_frame(gs_handle* h, const float* view, const float* proj, int32_t W, int32_t H,
-                              void* out_user, int32_t out_is_device, bool bgra8, void* stream, bool band = false) {
+                              void* out_user, int32_t out_is_device, bool bgra8, void* stream, bool band = false,
+                              float* depth_user = nullptr) {
     gs_status s = check_ready(h);
     if (s != GS_OK) return s;
     if (!view || !proj || !out_user || W <= 0 || H <= 0 || W > 65535 || H > 65535)
         return fail(GS_ERR_INVALID_ARG, "gs_render: bad arguments");
+    if (depth_user && (h->opt.cap > 0 || h->opt.mode == GS_MODE_MLAB))  // (before anything is queued)
+        return fail(GS_ERR_UNSUPPORTED, "gs_render_depth: tile and live50 modes without a fragment cap only");
+    // (the depth image of this frame only: cleared again on every way out)
+    struct DepthScope {
+        gs_handle* h;
+        ~DepthScope() { h->depth_out = nullptr; }
+    } depth_scope{h};
+    h->depth_out = nullptr;
     hipStream_t st = static_cast<hipStream_t>(stream);
     gs::FrameUniforms U = make_uniforms(view, proj, W, H);
     const uint32_t T = (uint32_t)(U.tiles_x * U.tiles_y);
@@ -1606,6 +1631,13 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
         GS_HIP(h->fb.reserve(bytes));
         out = h->fb.ptr;
     }
+    if (depth_user) {
+        h->depth_out = depth_user;
+        if (!out_is_device) {
+            GS_HIP(h->fbd.reserve((size_t)W * H * 4));
+            h->depth_out = h->fbd.as<float>();
+        }
+    }
     std::memset(&h->stats, 0, sizeof h->stats);
     h->shard_frame = false;
     // frames_in_flight 2: projection .. binning on the side stream, into the
@@ -1635,6 +1667,7 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
         GS_HIP(hipStreamWaitEvent(sp, h->sorted_ev, 0));
     }
     h->last_pipe = pipe;
+    if (h->depth_out) GS_HIP(h->cur.zf.reserve((size_t)std::max<int64_t>(h->n, 1) * 4));
     begin_frame(h, sp);
     // Bin-first frames of one GPU: the preprocess also sums every scan
     // block's pairs, fills the empty bin ranges and zeroes the first sort
@@ -1699,6 +1732,8 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
                                  h->cur.dkey.as<uint32_t>(), h->cur.rlo.as<uint32_t>(), h->cur.rhi.as<uint32_t>(), sp,
                                  kernel_event(h, 0), h->fused_prep.aux ? h->pre_ev : kernel_event(h, 1),
                                  fetch_counter(h), fuse));
+    // (depth frames: the splats' view depths, behind the projection on its stream)
+    if (h->depth_out) GS_HIP(gs::launch_zf_plane(h->scene_dev(), U, h->cur.zf.as<float>(), sp));
     mark(h, 1, sp);
     if ((s = bin_sort_composite(h, (uint32_t)h->n, h->cur.dkey.as<uint32_t>(), h->cur.rlo.as<uint32_t>(),
                                 h->cur.rhi.as<uint32_t>(), h->cur.rec.as<float4>(), gs::kRecFloat4, U, compact,
@@ -1709,6 +1744,8 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
     const uint64_t P = (uint64_t)h->stats.pairs;
     if (!out_is_device) {
         GS_HIP(hipMemcpyAsync(out_user, out, bytes, hipMemcpyDeviceToHost, st));
+        if (depth_user)
+            GS_HIP(hipMemcpyAsync(depth_user, h->depth_out, (size_t)W * H * 4, hipMemcpyDeviceToHost, st));
         GS_HIP(hipStreamSynchronize(st));
     }
     fill_stats(h, P, U);
@@ -1722,6 +1759,14 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
 gs_status gs_render(gs_handle* h, const float* view, const float* proj, int32_t W, int32_t H, float* out_rgba,
                     int32_t out_is_device, void* stream) {
     return render_frame(h, view, proj, W, H, out_rgba, out_is_device, false, stream);
+}
+
+gs_status gs_render_depth(gs_handle* h, const float* view, const float* proj, int32_t W, int32_t H, float* out_rgba,
+                          float* out_depth, int32_t out_is_device, void* stream) {
+    if (!h) return fail(GS_ERR_INVALID_ARG, "null handle");
+    if (!view || !proj || !out_rgba || !out_depth || W <= 0 || H <= 0 || W > 65535 || H > 65535)
+        return fail(GS_ERR_INVALID_ARG, "gs_render_depth: bad arguments");
+    return render_frame(h, view, proj, W, H, out_rgba, out_is_device, false, stream, false, out_depth);
 }
 
 gs_status gs_render_bgra8(gs_handle* h, const float* view, const float* proj, int32_t W, int32_t H,
@@ -1744,7 +1789,7 @@ gs_status gs_last_stats(gs_handle* h, gs_stats* out) {
         if (h->split_render) GS_HIP(hipEventSynchronize(h->comp_done));  // (its composite counts on its own stream)
         GS_HIP(hipMemcpy(&v, h->fetch.as<unsigned long long>() + 2 * h->stats_set, 8, hipMemcpyDeviceToHost));
         h->stats.records_fetched = (int64_t)v;
-        h->stats.bytes_composite = h->stats_fixed_bytes + (int64_t)v * (4 + 48);
+        h->stats.bytes_composite = h->stats_fixed_bytes + (int64_t)v * (4 + 48 + (h->stats_depth ? 4 : 0));
         if (h->stats.cut_frame) {
             // depth cuts: the front lists' pairs (the first sort pass reads all
             // P, counting and scattering, and writes the kept P1; the second

@@ -856,6 +856,8 @@ static hipError_t launch_mode(const CompositeArgs& a, hipStream_t st, hipEvent_t
 
 hipError_t launch_composite(const CompositeArgs& a, int mode, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
     const bool cap = a.cap > 0;
+    // depth frames: kernels of their own (composite_depth.hip); no cap, slabs or MLAB there
+    if (a.depth_out) return launch_composite_depth(a, mode, st, t0, t1);
     if (cap && !a.thr) return hipErrorInvalidValue;
     if (a.order && (a.rows || a.compact || a.nrows != a.tiles_y)) return hipErrorInvalidValue;  // (whole frames only)
     if (a.pass) {  // depth-cut frames: tile / live50 rules, no cap, no depth slabs (owned rows allowed)

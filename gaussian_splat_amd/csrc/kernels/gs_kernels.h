@@ -315,7 +315,23 @@ struct CompositeArgs {
     // (optional, strip composite pass 1) wcost[2 bin + half] = the records the
     // bin's top / bottom half workgroup fetched: launch_order_bins' costs
     uint32_t* wcost;
+    // Depth frames (gs_render_depth; tile / live50 rules on
+    // fp32 frames, no cap, no slabs): with depth_out set the depth composites
+    // run (composite_depth.hip) and write, beside every colour pixel, D =
+    // the per-splat view depth zf[id] (launch_zf_plane; parallel to rec)
+    // accumulated as a fourth colour channel.  Depth-cut passes keep an open
+    // quadrant's D in state_d (a float per pixel, beside `state`).
+    const float* zf;
+    float* depth_out;
+    float* state_d;
 };
+// zf[i] = -xform_row(U.V, 2, x, y, z) for every splat of the scene: the
+// projection's own fp32 view depth (also of culled splats, which no list
+// holds).  Queued after the preprocess of a depth frame, on its stream.
+hipError_t launch_zf_plane(const SceneDev& s, const FrameUniforms& U, float* zf, hipStream_t st);
+// launch_composite's depth variants (it forwards here when a.depth_out is set).
+hipError_t launch_composite_depth(const CompositeArgs& a, int mode, hipStream_t st, hipEvent_t t0 = nullptr,
+                                  hipEvent_t t1 = nullptr);
 // One 256-lane workgroup per owned 16x16 tile.  mode 0 = tile rule (A >= 0.99
 // break), 1 = live50 rule (T < 0.01 break), 2 = MLAB k-buffer (a.vals
 // index-ordered, a.dkey set, no cap); with a.cap > 0 only fragments with

@@ -197,6 +197,20 @@ gs_status gs_render(gs_handle *h, const float view[16], const float proj[16], in
  * converted inside the composite (clamp [0,1], x255, round to nearest even). */
 gs_status gs_render_bgra8(gs_handle *h, const float view[16], const float proj[16], int32_t width,
                           int32_t height, uint8_t *out_bgra, int32_t out_is_device, void *hip_stream);
+/* Colour frame as gs_render, plus out_depth: width*height float32, row-major,
+ * y down, from the same composite pass.  out_depth[p] is the accumulated,
+ * unnormalised view depth D of the pixel: composited exactly as a colour
+ * channel whose per-splat value is the projection's fp32 zF (the same
+ * fragments, order, weights and break rule; 0.0 where no fragment lands;
+ * DESIGN.md §2.11).  In tile mode the expected depth is D / A with A the colour
+ * frame's alpha; the division is the caller's.  out_rgba is bit-identical to
+ * gs_render's, and the two calls may alternate freely on one handle.
+ * Tile and live50 modes with cap == 0 (any depth_split, binning,
+ * frames_in_flight, SH degree); cap > 0 or MLAB mode: GS_ERR_UNSUPPORTED,
+ * nothing is enqueued.  (Added without an ABI version change: an addition.) */
+gs_status gs_render_depth(gs_handle *h, const float view[16], const float proj[16], int32_t width,
+                          int32_t height, float *out_rgba, float *out_depth, int32_t out_is_device,
+                          void *hip_stream);
 gs_status gs_last_stats(gs_handle *h, gs_stats *out);
 /* stage_timing 2: preprocess and composite kernel times (ms, from the events
  * in their dispatch packets) of the last min(max_frames, 64) frames rendered

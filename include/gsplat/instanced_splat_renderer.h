@@ -42,6 +42,11 @@ public:
     void renderBGRA8(void* commandBuffer, void* drawableTexture, const simd_float4x4& viewMatrix,
                      const simd_float4x4& projectionMatrix, float viewportWidth, float viewportHeight);
 
+    // Addition (not in the reference): render() plus the accumulated depth image
+    // (width*height floats in HBM) from the same composite pass (gs_render_depth).
+    void renderDepth(void* commandBuffer, void* drawableTexture, void* depthTexture, const simd_float4x4& viewMatrix,
+                     const simd_float4x4& projectionMatrix, float viewportWidth, float viewportHeight);
+
     // Additions (not in the reference): status of the last call, frame stats.
     gs_status lastStatus() const { return status_; }
     gs_stats lastStats() const;
