@@ -251,6 +251,7 @@ struct gs_group {
     std::vector<ncclComm_t> comms;
     Pool* pool = nullptr;
     hipEvent_t frame_done = nullptr;  // on devices[0]: everything of the last frame
+    hipEvent_t caller_ready = nullptr;  // on devices[0]: what the caller's stream held when a pipelined call began
     DevMem fb;                        // host-output frames
     int64_t timeout_ms = 60000;       // bound of every host wait (gs_group_set_timeout)
     bool timeout_set = false;         // set by gs_group_set_timeout (GS_COMM_TIMEOUT_MS then ignored)
@@ -287,6 +288,7 @@ struct gs_group {
         gscomm::destroy_all(comms, [](ncclComm_t c) { return g_rccl.comm_destroy(c); });
         gscomm::destroy_all(xcomms, [](ncclComm_t c) { return g_rccl.comm_destroy(c); });
         if (frame_done) (void)hipEventDestroy(frame_done);
+        if (caller_ready) (void)hipEventDestroy(caller_ready);
         fb.release();
     }
 };
@@ -742,6 +744,9 @@ gs_status gather_pipelined(gs_group* g, int Wd, int Ht, float* out, hipStream_t 
     }
     GG_HIP(hipSetDevice(r0.dev));
     for (int d = 1; d < W; ++d) GG_HIP(hipStreamWaitEvent(r0.gs, g->r[(size_t)d].ev_done, 0));
+    // (`out` is the caller's: whatever their stream still held that reads or
+    // writes it when the call began comes first)
+    GG_HIP(hipStreamWaitEvent(r0.gs, g->caller_ready, 0));
     if (g->transport == GS_TRANSPORT_RCCL) {
         GG_NCCL(g_rccl.group_start());
         for (int d = 1; d < W; ++d) {
@@ -1061,6 +1066,10 @@ gs_status pipelined_call(gs_group* g, const float* view, const float* proj, int3
     Rank& r0 = g->r[0];
     GG_HIP(hipSetDevice(r0.dev));
     hipStream_t user = static_cast<hipStream_t>(hip_stream);
+    // (rank 0's gather stream writes `out`: it starts after the work the
+    // caller's stream holds now, gather_pipelined)
+    if (!g->caller_ready) GG_HIP(hipEventCreateWithFlags(&g->caller_ready, hipEventDisableTiming));
+    GG_HIP(hipEventRecord(g->caller_ready, user));
     const int ow = g->pend.on ? g->pend.width : width, oh = g->pend.on ? g->pend.height : height;
     const size_t bytes = (size_t)ow * oh * 16;
     float* out = out_rgba;
