@@ -28,6 +28,7 @@ RECORD_DTYPE = np.dtype([("cx", "<f4"), ("cy", "<f4"), ("ax", "<f4"), ("ay", "<f
                          ("rect_lo", "<u4"), ("rect_hi", "<u4")])
 MODES = {"tile": 0, "live50": 1, "mlab": 2}
 BINNING = {"default": 0, "depth_first": 1, "bin_first": 2}  # gs_binning
+MAX_FEATURE_CHANNELS = 64  # GS_MAX_FEATURE_CHANNELS (gs_render_features)
 
 
 def _mat16(m) -> C.Array:
@@ -310,6 +311,73 @@ class InstancedSplatRenderer:
         check(lib().gs_render_depth(self._h, _mat16(view), _mat16(proj), int(width), int(height), out.ctypes.data,
                                     depth.ctypes.data, 0, None), "gs_render_depth")
         return out, depth
+
+    def _feature_shape(self, features):
+        """(N, K) of a feature matrix for this handle, or ValueError."""
+        if getattr(features, "ndim", None) != 2:
+            raise ValueError("features must be 2-D (N, K), one row per splat")
+        n, k = int(features.shape[0]), int(features.shape[1])
+        if n != self.getPointCount():
+            raise ValueError(f"features has {n} rows, the scene has {self.getPointCount()} splats")
+        if not 1 <= k <= MAX_FEATURE_CHANNELS:
+            raise ValueError(f"features has {k} channels, 1..{MAX_FEATURE_CHANNELS} are supported")
+        return n, k
+
+    def render_features(self, view, proj, width: int, height: int, features, out=None, out_features=None,
+                        stream=None):
+        """Render colour and K per-splat feature channels composited per pixel
+        (gs_render_features): returns (rgba, feats), torch float32 CUDA tensors
+        (H, W, 4) and (H, W, K).  `features` is a torch float32 CUDA tensor (N, K),
+        contiguous, row i for splat i of the loaded scene (get_scene's order);
+        feats[y, x, k] is features[:, k] composited exactly as a colour channel
+        (same fragments, order, weights and break rule; 0 where nothing lands; not
+        clamped, not normalised).  `rgba` is render()'s frame bit for bit.  Tile and
+        live50 modes without a fragment cap; the frame builds whole bin lists
+        whatever depth_split says."""
+        import torch
+
+        if not isinstance(features, torch.Tensor):
+            raise ValueError("features must be a torch tensor")
+        n, k = self._feature_shape(features)
+        if features.dtype != torch.float32:
+            raise ValueError(f"features must be float32, got {features.dtype}")
+        if not features.is_contiguous():
+            raise ValueError("features must be contiguous")
+        dev = torch.device(f"cuda:{self.device or 0}")
+        if not features.is_cuda or features.device != dev:
+            raise ValueError(f"features must be on the handle's device {dev}, got {features.device}")
+        if out is None:
+            out = torch.empty((height, width, 4), dtype=torch.float32, device=dev)
+        if out_features is None:
+            out_features = torch.empty((height, width, k), dtype=torch.float32, device=dev)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == width * height * 4
+        assert (out_features.is_cuda and out_features.dtype == torch.float32 and out_features.is_contiguous()
+                and out_features.numel() == width * height * k)
+        assert out.device == dev and out_features.device == dev
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device).cuda_stream
+        check(lib().gs_render_features(self._h, _mat16(view), _mat16(proj), int(width), int(height),
+                                       C.c_void_p(features.data_ptr() if n else None), k, C.c_void_p(out.data_ptr()),
+                                       C.c_void_p(out_features.data_ptr()), 1, C.c_void_p(stream)),
+              "gs_render_features")
+        return out, out_features
+
+    def render_features_host(self, view, proj, width: int, height: int, features):
+        """render_features from and into host memory: `features` a numpy float32
+        array (N, K), C-contiguous; returns (rgba (H, W, 4), feats (H, W, K)) numpy float32."""
+        if not isinstance(features, np.ndarray):
+            raise ValueError("features must be a numpy array")
+        n, k = self._feature_shape(features)
+        if features.dtype != np.float32:
+            raise ValueError(f"features must be float32, got {features.dtype}")
+        if not features.flags["C_CONTIGUOUS"]:
+            raise ValueError("features must be C-contiguous")
+        out = np.empty((height, width, 4), np.float32)
+        feats = np.empty((height, width, k), np.float32)
+        check(lib().gs_render_features(self._h, _mat16(view), _mat16(proj), int(width), int(height),
+                                       features.ctypes.data if n else None, k, out.ctypes.data, feats.ctypes.data, 0,
+                                       None), "gs_render_features")
+        return out, feats
 
     def render_bgra8(self, view, proj, width: int, height: int, out=None, stream=None):
         """Render as BGRA8Unorm (the reference's drawable format) into `out`

@@ -49,6 +49,17 @@ void InstancedSplatRenderer::renderDepth(void* commandBuffer, void* drawableText
                               static_cast<float*>(depthTexture), 1, commandBuffer);
 }
 
+void InstancedSplatRenderer::renderFeatures(void* commandBuffer, void* drawableTexture, void* featureTexture,
+                                            const float* features, int channels, const simd_float4x4& viewMatrix,
+                                            const simd_float4x4& projectionMatrix, float viewportWidth,
+                                            float viewportHeight) {
+    if (!handle_ || gs_point_count(handle_) == 0 || !drawableTexture || !featureTexture) return;
+    status_ = gs_render_features(handle_, viewMatrix.data(), projectionMatrix.data(), (int32_t)viewportWidth,
+                                 (int32_t)viewportHeight, features, (int32_t)channels,
+                                 static_cast<float*>(drawableTexture), static_cast<float*>(featureTexture), 1,
+                                 commandBuffer);
+}
+
 int InstancedSplatRenderer::getPointCount() const { return (int)gs_point_count(handle_); }
 
 gs_stats InstancedSplatRenderer::lastStats() const {

@@ -118,6 +118,16 @@ struct gs_handle {
     float* depth_out = nullptr;
     bool stats_depth = false;  // the frame in `stats` was a depth frame
     DevBuf fbd, dstate;
+    // Feature frames (gs_render_features).  feat_in / feat_out
+    // / feat_k: the device feature matrix, the device feature image and K of
+    // the frame being enqueued (feat_out null: not a feature frame), set and
+    // cleared by render_frame; featbuf, fbf: their staging copies for host
+    // input and output (the call syncs, so one of each serves every frame).
+    const float* feat_in = nullptr;
+    float* feat_out = nullptr;
+    int feat_k = 0;
+    int64_t stats_rec_bytes = 52;  // composite bytes per fetched record of the frame in `stats`
+    DevBuf featbuf, fbf;
     DevBuf dsk, dso, dsl, dsh, dtk, dto, dtl, dth;  // depth sort: keys, order, rect lo/hi (+ ping-pong)
     DevBuf xmask, xcounts, xtotal;  // multi-GPU exchange
     // depth-slab frames: full-frame ownership; the colour pass
@@ -1174,6 +1184,9 @@ gs_status bin_sort_composite(gs_handle* h, uint32_t m, const uint32_t* dkey, con
             mark(h, 6, sd);
             GS_HIP(handoff(true));
             GS_HIP(gs::launch_composite(c, h->opt.mode, sc, kernel_event(h, 2), kernel_event(h, 3)));
+            // (feature frames: the passes over the same whole lists, behind the colour composite)
+            if (h->feat_out)
+                GS_HIP(gs::launch_composite_features(c, h->feat_in, h->feat_out, h->feat_k, h->opt.mode, sc));
             if (slab_t) {
                 h->slab_ca = c;
                 h->slab_lists = true;
@@ -1268,6 +1281,8 @@ gs_status bin_sort_composite(gs_handle* h, uint32_t m, const uint32_t* dkey, con
     GS_HIP(handoff());
     ca.fetched = fetch_counter(h);
     GS_HIP(gs::launch_composite(ca, h->opt.mode, sc, kernel_event(h, 2), kernel_event(h, 3)));
+    if (h->feat_out)  // (feature frames, as in the bin-first tail)
+        GS_HIP(gs::launch_composite_features(ca, h->feat_in, h->feat_out, h->feat_k, h->opt.mode, sc));
     if (slab_t) {
         h->slab_ca = ca;
         h->slab_lists = true;
@@ -1322,7 +1337,16 @@ void fill_stats(gs_handle* h, uint64_t P, const gs::FrameUniforms& U) {
     h->stats_depth = h->depth_out != nullptr;
     h->stats_fixed_bytes = 4 * T * 8 + (int64_t)U.width * U.height * (h->stats_depth ? 20 : 16);
     h->stats_set = h->set;
-    s.bytes_composite = h->stats_fixed_bytes + 4 * Pi * (4 + 48 + (h->stats_depth ? 4 : 0));
+    // (a feature frame: each of its ceil(K / 4) passes reads the range words and the fetched
+    // records again, with 16 B of values per record instead of the whole row: 4 K over the
+    // passes; and the feature image)
+    h->stats_rec_bytes = 4 + 48 + (h->stats_depth ? 4 : 0);
+    if (h->feat_out) {
+        const int64_t K = h->feat_k, passes = (K + 3) / 4;
+        h->stats_fixed_bytes += passes * 4 * T * 8 + 4 * K * (int64_t)U.width * U.height;
+        h->stats_rec_bytes += passes * (4 + 48) + 4 * K;
+    }
+    s.bytes_composite = h->stats_fixed_bytes + 4 * Pi * h->stats_rec_bytes;
     s.records_fetched = -1;
     s.pairs_sorted = Pi;
     s.cut_frame = h->cut_frame ? 1 : 0;
@@ -1580,21 +1604,40 @@ gs_status gs_set_cap(gs_handle* h, int32_t cap) {
 // bgra8, packed BGRA8Unorm (4 B/pixel, converted inside the composite).
 // depth_user (gs_render_depth; fp32 RGBA frames): also the accumulated depth
 // image, W * H floats, from the same composite pass.
+// feat (gs_render_features; fp32 RGBA frames): also the feature image, W * H *
+// channels floats, from passes behind the colour composite;
+// its buffers are the caller's kind (out_is_device).
+struct FeatureCall {
+    const float* features;  // [n][channels]
+    int32_t channels;
+    float* out;             // [H][W][channels]
+};
 static gs_status render_frame(gs_handle* h, const float* view, const float* proj, int32_t W, int32_t H,
                               void* out_user, int32_t out_is_device, bool bgra8, void* stream, bool band = false,
-                              float* depth_user = nullptr) {
+                              float* depth_user = nullptr, const FeatureCall* feat = nullptr) {
     gs_status s = check_ready(h);
     if (s != GS_OK) return s;
     if (!view || !proj || !out_user || W <= 0 || H <= 0 || W > 65535 || H > 65535)
         return fail(GS_ERR_INVALID_ARG, "gs_render: bad arguments");
     if (depth_user && (h->opt.cap > 0 || h->opt.mode == GS_MODE_MLAB))  // (before anything is queued)
         return fail(GS_ERR_UNSUPPORTED, "gs_render_depth: tile and live50 modes without a fragment cap only");
-    // (the depth image of this frame only: cleared again on every way out)
+    if (feat && (h->opt.cap > 0 || h->opt.mode == GS_MODE_MLAB))  // (before anything is queued)
+        return fail(GS_ERR_UNSUPPORTED, "gs_render_features: tile and live50 modes without a fragment cap only");
+    if (feat && h->world != 1) return fail(GS_ERR_UNSUPPORTED, "gs_render_features: single-GPU handles only");
+    // (the depth and feature images of this frame only: cleared again on every way out)
     struct DepthScope {
         gs_handle* h;
-        ~DepthScope() { h->depth_out = nullptr; }
+        ~DepthScope() {
+            h->depth_out = nullptr;
+            h->feat_in = nullptr;
+            h->feat_out = nullptr;
+            h->feat_k = 0;
+        }
     } depth_scope{h};
     h->depth_out = nullptr;
+    h->feat_in = nullptr;
+    h->feat_out = nullptr;
+    h->feat_k = 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     gs::FrameUniforms U = make_uniforms(view, proj, W, H);
     const uint32_t T = (uint32_t)(U.tiles_x * U.tiles_y);
@@ -1638,6 +1681,21 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
             h->depth_out = h->fbd.as<float>();
         }
     }
+    const size_t feat_bytes = feat ? (size_t)W * H * (size_t)feat->channels * 4 : 0;
+    if (feat) {
+        h->feat_in = feat->features;
+        h->feat_out = feat->out;
+        h->feat_k = feat->channels;
+        if (!out_is_device) {
+            // (host calls sync before they return, so the staging copies are free here)
+            const size_t in_bytes = (size_t)h->n * (size_t)feat->channels * 4;
+            GS_HIP(h->featbuf.reserve(std::max<size_t>(in_bytes, 16)));
+            GS_HIP(h->fbf.reserve(feat_bytes));
+            if (in_bytes) GS_HIP(hipMemcpyAsync(h->featbuf.ptr, feat->features, in_bytes, hipMemcpyHostToDevice, st));
+            h->feat_in = h->featbuf.as<float>();
+            h->feat_out = h->fbf.as<float>();
+        }
+    }
     std::memset(&h->stats, 0, sizeof h->stats);
     h->shard_frame = false;
     // frames_in_flight 2: projection .. binning on the side stream, into the
@@ -1677,7 +1735,9 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
     h->fused_prep = gs_handle::ListPrep{};
     h->order_pick = -1;
     const bool whole = band ? h->band_local : h->world == 1;  // (the binning owns every row it sees)
-    const bool cut_on = depth_cuts_on(h) && whole && cut_rule(h, U);
+    // (a feature frame is a whole-list frame whatever depth_split says: its passes read the
+    // whole lists, and the set's cut tables are invalidated as by any uncut frame)
+    const bool cut_on = depth_cuts_on(h) && whole && cut_rule(h, U) && !h->feat_out;
     bool cut_frame = false;
     if (whole && h->n > 0 && h->opt.mode != GS_MODE_MLAB) {
         const bool bf = bin_first_order(h, U, (uint32_t)h->n, h->band_local ? band_nrows : -1, cut_on);
@@ -1746,6 +1806,7 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
         GS_HIP(hipMemcpyAsync(out_user, out, bytes, hipMemcpyDeviceToHost, st));
         if (depth_user)
             GS_HIP(hipMemcpyAsync(depth_user, h->depth_out, (size_t)W * H * 4, hipMemcpyDeviceToHost, st));
+        if (feat) GS_HIP(hipMemcpyAsync(feat->out, h->feat_out, feat_bytes, hipMemcpyDeviceToHost, st));
         GS_HIP(hipStreamSynchronize(st));
     }
     fill_stats(h, P, U);
@@ -1769,6 +1830,23 @@ gs_status gs_render_depth(gs_handle* h, const float* view, const float* proj, in
     return render_frame(h, view, proj, W, H, out_rgba, out_is_device, false, stream, false, out_depth);
 }
 
+static_assert(GS_MAX_FEATURE_CHANNELS == gs::kMaxFeatureChannels, "feature channel limit");
+
+gs_status gs_render_features(gs_handle* h, const float* view, const float* proj, int32_t W, int32_t H,
+                             const float* features, int32_t channels, float* out_rgba, float* out_features,
+                             int32_t is_device, void* stream) {
+    // (the arguments are judged first, also on a handle that was never initialised)
+    if (!h) return fail(GS_ERR_INVALID_ARG, "gs_render_features: null handle");
+    if (!view || !proj || !out_rgba || !out_features || W <= 0 || H <= 0 || W > 65535 || H > 65535)
+        return fail(GS_ERR_INVALID_ARG, "gs_render_features: bad arguments");
+    if (channels < 1 || channels > GS_MAX_FEATURE_CHANNELS)
+        return fail(GS_ERR_INVALID_ARG, "gs_render_features: channels must be 1.." +
+                                            std::to_string(GS_MAX_FEATURE_CHANNELS) + ", got " + std::to_string(channels));
+    if (!features && h->n > 0) return fail(GS_ERR_INVALID_ARG, "gs_render_features: null features");
+    const FeatureCall fc{features, channels, out_features};
+    return render_frame(h, view, proj, W, H, out_rgba, is_device, false, stream, false, nullptr, &fc);
+}
+
 gs_status gs_render_bgra8(gs_handle* h, const float* view, const float* proj, int32_t W, int32_t H,
                           uint8_t* out_bgra, int32_t out_is_device, void* stream) {
     return render_frame(h, view, proj, W, H, out_bgra, out_is_device, true, stream);
@@ -1789,7 +1867,7 @@ gs_status gs_last_stats(gs_handle* h, gs_stats* out) {
         if (h->split_render) GS_HIP(hipEventSynchronize(h->comp_done));  // (its composite counts on its own stream)
         GS_HIP(hipMemcpy(&v, h->fetch.as<unsigned long long>() + 2 * h->stats_set, 8, hipMemcpyDeviceToHost));
         h->stats.records_fetched = (int64_t)v;
-        h->stats.bytes_composite = h->stats_fixed_bytes + (int64_t)v * (4 + 48 + (h->stats_depth ? 4 : 0));
+        h->stats.bytes_composite = h->stats_fixed_bytes + (int64_t)v * h->stats_rec_bytes;
         if (h->stats.cut_frame) {
             // depth cuts: the front lists' pairs (the first sort pass reads all
             // P, counting and scattering, and writes the kept P1; the second

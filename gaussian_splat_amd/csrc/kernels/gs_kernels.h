@@ -332,6 +332,25 @@ hipError_t launch_zf_plane(const SceneDev& s, const FrameUniforms& U, float* zf,
 // launch_composite's depth variants (it forwards here when a.depth_out is set).
 hipError_t launch_composite_depth(const CompositeArgs& a, int mode, hipStream_t st, hipEvent_t t0 = nullptr,
                                   hipEvent_t t1 = nullptr);
+// Feature frames (gs_render_features; composite_features.hip):
+// the second parameter of the feature composites, beside CompositeArgs (which
+// the colour and depth kernels take by value and which stays as it is).
+constexpr int kMaxFeatureChannels = 64;  // (gsplat.h GS_MAX_FEATURE_CHANNELS)
+struct FeatureArgs {
+    const float* feat;  // [n][channels] per-splat values, row i for splat i
+    float* out;         // [height][width][channels] image
+    int channels;       // K
+    int first;          // the launch composites channels first .. first + 3 (those below K)
+};
+// out[pixel][k] = features[.][k] composited as a colour channel, for every k
+// in [0, channels): ceil(channels / 4) launches of four channels each, over
+// the whole lists a (vals, ranges, rec; pass 0, every bin row, tile / live50
+// rules, no cap) the frame's colour composite has just read, on its stream.
+// a.out, a.fetched and the depth fields are not used.  feat and out need only
+// 4-B alignment; 16-B aligned ones with channels % 4 == 0 take 16-B loads and
+// stores.  Rows of splats in no list are never read.
+hipError_t launch_composite_features(const CompositeArgs& a, const float* feat, float* out, int channels, int mode,
+                                     hipStream_t st);
 // One 256-lane workgroup per owned 16x16 tile.  mode 0 = tile rule (A >= 0.99
 // break), 1 = live50 rule (T < 0.01 break), 2 = MLAB k-buffer (a.vals
 // index-ordered, a.dkey set, no cap); with a.cap > 0 only fragments with

@@ -211,6 +211,33 @@ gs_status gs_render_bgra8(gs_handle *h, const float view[16], const float proj[1
 gs_status gs_render_depth(gs_handle *h, const float view[16], const float proj[16], int32_t width,
                           int32_t height, float *out_rgba, float *out_depth, int32_t out_is_device,
                           void *hip_stream);
+/* Colour frame as gs_render, plus out_features: width*height*channels float32,
+ * row-major, y down, channels innermost.  features: gs_point_count(h) x
+ * channels float32, row-major; row i belongs to splat i of the loaded
+ * (post-crop) scene, in gs_get_scene's order.  For every pixel and channel k,
+ * out_features[p][k] is composited exactly as a colour channel whose
+ * per-splat value is features[i][k]: the same fragments, order, weights and
+ * break rule as the colour channels, from 0.0; not clamped, not normalised
+ * (0.0 where no fragment lands; NaN and infinite values propagate into their
+ * channel only).  Depth is the case channels = 1, f = zF.
+ * Rows of splats that reach no bin list (culled, off-screen) are never read
+ * for any pixel's value, and nothing outside the matrix is read.
+ * 1 <= channels <= GS_MAX_FEATURE_CHANNELS; features may be NULL only for a
+ * scene of 0 splats.  is_device covers features, out_rgba and out_features
+ * (1: HBM pointers, async on `hip_stream`, features must stay unchanged until
+ * the frame is done; 0: host pointers, the call syncs); the three buffers
+ * must not overlap; 4-byte alignment is enough.  out_rgba is bit-identical to
+ * gs_render's, and gs_render, gs_render_depth and gs_render_features may
+ * alternate freely on one handle.  A feature frame builds whole bin lists
+ * whatever gs_options.depth_split says (gs_stats.cut_frame == 0), so the next
+ * colour frames on its buffer set learn their depth cuts again.
+ * Tile and live50 modes with cap == 0 on a single-GPU handle; cap > 0, MLAB
+ * mode or a sharded handle: GS_ERR_UNSUPPORTED, nothing is enqueued.
+ * (Added without an ABI version change: an addition.) */
+#define GS_MAX_FEATURE_CHANNELS 64
+gs_status gs_render_features(gs_handle *h, const float view[16], const float proj[16], int32_t width,
+                             int32_t height, const float *features, int32_t channels, float *out_rgba,
+                             float *out_features, int32_t is_device, void *hip_stream);
 gs_status gs_last_stats(gs_handle *h, gs_stats *out);
 /* stage_timing 2: preprocess and composite kernel times (ms, from the events
  * in their dispatch packets) of the last min(max_frames, 64) frames rendered

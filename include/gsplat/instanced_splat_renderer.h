@@ -47,6 +47,14 @@ public:
     void renderDepth(void* commandBuffer, void* drawableTexture, void* depthTexture, const simd_float4x4& viewMatrix,
                      const simd_float4x4& projectionMatrix, float viewportWidth, float viewportHeight);
 
+    // Addition (not in the reference): render() plus `channels` per-splat feature
+    // channels composited per pixel (gs_render_features): features is the
+    // getPointCount() x channels float matrix in HBM, featureTexture the
+    // width*height*channels float image in HBM, channels innermost.
+    void renderFeatures(void* commandBuffer, void* drawableTexture, void* featureTexture, const float* features,
+                        int channels, const simd_float4x4& viewMatrix, const simd_float4x4& projectionMatrix,
+                        float viewportWidth, float viewportHeight);
+
     // Additions (not in the reference): status of the last call, frame stats.
     gs_status lastStatus() const { return status_; }
     gs_stats lastStats() const;
