@@ -379,6 +379,119 @@ class InstancedSplatRenderer:
                                        None), "gs_render_features")
         return out, feats
 
+    def render_contrib(self, view, proj, width: int, height: int, mask=None, out=None, sum=None, count=None,
+                       max=None, accumulate: bool = False, stream=None):
+        """Render colour and each splat's blend weight totals over the frame
+        (gs_render_contrib): returns (rgba, sum, count, max).  For splat i of the
+        loaded scene (get_scene's order) and every pixel the splat is composited at,
+        the weight that multiplies its colour there is quantised to q = 0 .. 2**24;
+        sum[i] is the total of q (torch.int64; sum / 2**24 is the splat's weight in
+        pixels), count[i] the pixels with q > 0 and max[i] the largest q (torch.int32,
+        holding the uint32 bits), CUDA tensors of N entries.  `mask`: a torch.uint8 or
+        torch.bool (H, W) contiguous CUDA tensor of the pixels that count (None: all).
+        accumulate=True combines the frame's totals into the three given tensors
+        (sum +=, count +=, max = max) instead of overwriting them.  `rgba` is
+        render()'s frame bit for bit.  Tile and live50 modes without a fragment cap;
+        the frame builds whole bin lists whatever depth_split says."""
+        import torch
+
+        n = self.getPointCount()
+        dev = torch.device(f"cuda:{self.device or 0}")
+        if accumulate and (sum is None or count is None or max is None):
+            raise ValueError("accumulate=True needs the sum, count and max tensors to combine into")
+
+        def arr(t, name, dtype):
+            if t is None:  # (allocated once every argument is judged)
+                return None
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be a torch tensor")
+            if t.dtype != dtype:
+                raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+            if tuple(t.shape) != (n,):
+                raise ValueError(f"{name} must have shape ({n},), got {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            if not t.is_cuda or t.device != dev:
+                raise ValueError(f"{name} must be on the handle's device {dev}, got {t.device}")
+            return t
+
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor):
+                raise ValueError("mask must be a torch tensor")
+            if mask.dtype not in (torch.uint8, torch.bool):
+                raise ValueError(f"mask must be uint8 or bool, got {mask.dtype}")
+            if tuple(mask.shape) != (height, width):
+                raise ValueError(f"mask must have shape ({height}, {width}), got {tuple(mask.shape)}")
+            if not mask.is_contiguous():
+                raise ValueError("mask must be contiguous")
+            if not mask.is_cuda or mask.device != dev:
+                raise ValueError(f"mask must be on the handle's device {dev}, got {mask.device}")
+        sum = arr(sum, "sum", torch.int64)
+        count = arr(count, "count", torch.int32)
+        max = arr(max, "max", torch.int32)
+        if sum is None:
+            sum = torch.empty((n,), dtype=torch.int64, device=dev)
+        if count is None:
+            count = torch.empty((n,), dtype=torch.int32, device=dev)
+        if max is None:
+            max = torch.empty((n,), dtype=torch.int32, device=dev)
+        if out is None:
+            out = torch.empty((height, width, 4), dtype=torch.float32, device=dev)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == width * height * 4
+        assert out.device == dev
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device).cuda_stream
+        check(lib().gs_render_contrib(self._h, _mat16(view), _mat16(proj), int(width), int(height),
+                                      C.c_void_p(mask.data_ptr() if mask is not None else None),
+                                      C.c_void_p(out.data_ptr()), C.c_void_p(sum.data_ptr() if n else None),
+                                      C.c_void_p(count.data_ptr() if n else None),
+                                      C.c_void_p(max.data_ptr() if n else None), 1 if accumulate else 0, 1,
+                                      C.c_void_p(stream)), "gs_render_contrib")
+        return out, sum, count, max
+
+    def render_contrib_host(self, view, proj, width: int, height: int, mask=None, sum=None, count=None, max=None,
+                            accumulate: bool = False):
+        """render_contrib from and into host memory: `mask` a numpy uint8 / bool array
+        (H, W), C-contiguous, or None; returns (rgba (H, W, 4) float32, sum uint64,
+        count uint32, max uint32) numpy arrays; accumulate=True combines into the three
+        given arrays."""
+        n = self.getPointCount()
+        if accumulate and (sum is None or count is None or max is None):
+            raise ValueError("accumulate=True needs the sum, count and max arrays to combine into")
+
+        def arr(a, name, dtype):
+            if a is None:
+                return np.empty((n,), dtype)
+            if not isinstance(a, np.ndarray):
+                raise ValueError(f"{name} must be a numpy array")
+            if a.dtype != dtype:
+                raise ValueError(f"{name} must be {np.dtype(dtype)}, got {a.dtype}")
+            if a.shape != (n,):
+                raise ValueError(f"{name} must have shape ({n},), got {a.shape}")
+            if not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
+                raise ValueError(f"{name} must be C-contiguous and writeable")
+            return a
+
+        if mask is not None:
+            if not isinstance(mask, np.ndarray):
+                raise ValueError("mask must be a numpy array")
+            if mask.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+                raise ValueError(f"mask must be uint8 or bool, got {mask.dtype}")
+            if mask.shape != (height, width):
+                raise ValueError(f"mask must have shape ({height}, {width}), got {mask.shape}")
+            if not mask.flags["C_CONTIGUOUS"]:
+                raise ValueError("mask must be C-contiguous")
+        sum = arr(sum, "sum", np.uint64)
+        count = arr(count, "count", np.uint32)
+        max = arr(max, "max", np.uint32)
+        out = np.empty((height, width, 4), np.float32)
+        check(lib().gs_render_contrib(self._h, _mat16(view), _mat16(proj), int(width), int(height),
+                                      mask.ctypes.data if mask is not None else None, out.ctypes.data,
+                                      sum.ctypes.data if n else None, count.ctypes.data if n else None,
+                                      max.ctypes.data if n else None, 1 if accumulate else 0, 0, None),
+              "gs_render_contrib")
+        return out, sum, count, max
+
     def render_bgra8(self, view, proj, width: int, height: int, out=None, stream=None):
         """Render as BGRA8Unorm (the reference's drawable format) into `out`
         (torch uint8 CUDA tensor (H, W, 4), bytes B, G, R, A); returns it."""

@@ -60,6 +60,16 @@ void InstancedSplatRenderer::renderFeatures(void* commandBuffer, void* drawableT
                                  commandBuffer);
 }
 
+void InstancedSplatRenderer::renderContrib(void* commandBuffer, void* drawableTexture, const uint8_t* mask,
+                                           uint64_t* sum, uint32_t* count, uint32_t* max, bool accumulate,
+                                           const simd_float4x4& viewMatrix, const simd_float4x4& projectionMatrix,
+                                           float viewportWidth, float viewportHeight) {
+    if (!handle_ || gs_point_count(handle_) == 0 || !drawableTexture || !sum || !count || !max) return;
+    status_ = gs_render_contrib(handle_, viewMatrix.data(), projectionMatrix.data(), (int32_t)viewportWidth,
+                                (int32_t)viewportHeight, mask, static_cast<float*>(drawableTexture), sum, count, max,
+                                accumulate ? 1 : 0, 1, commandBuffer);
+}
+
 int InstancedSplatRenderer::getPointCount() const { return (int)gs_point_count(handle_); }
 
 gs_stats InstancedSplatRenderer::lastStats() const {

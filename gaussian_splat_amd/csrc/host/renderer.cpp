@@ -128,6 +128,14 @@ struct gs_handle {
     int feat_k = 0;
     int64_t stats_rec_bytes = 52;  // composite bytes per fetched record of the frame in `stats`
     DevBuf featbuf, fbf;
+    // Contrib frames (gs_render_contrib).  contrib: the device
+    // mask and the three device arrays of the frame being enqueued (contrib_on
+    // false: not a contrib frame), set and cleared by render_frame; cmask,
+    // csum, ccount, cmax: their staging copies for host calls (the call syncs,
+    // so one of each serves every frame; they only grow).
+    gs::ContribArgs contrib{};
+    bool contrib_on = false;
+    DevBuf cmask, csum, ccount, cmax;
     DevBuf dsk, dso, dsl, dsh, dtk, dto, dtl, dth;  // depth sort: keys, order, rect lo/hi (+ ping-pong)
     DevBuf xmask, xcounts, xtotal;  // multi-GPU exchange
     // depth-slab frames: full-frame ownership; the colour pass
@@ -1187,6 +1195,8 @@ gs_status bin_sort_composite(gs_handle* h, uint32_t m, const uint32_t* dkey, con
             // (feature frames: the passes over the same whole lists, behind the colour composite)
             if (h->feat_out)
                 GS_HIP(gs::launch_composite_features(c, h->feat_in, h->feat_out, h->feat_k, h->opt.mode, sc));
+            // (contrib frames: the scatter pass, in the same place)
+            if (h->contrib_on && m > 0) GS_HIP(gs::launch_composite_contrib(c, h->contrib, h->opt.mode, sc));
             if (slab_t) {
                 h->slab_ca = c;
                 h->slab_lists = true;
@@ -1283,6 +1293,7 @@ gs_status bin_sort_composite(gs_handle* h, uint32_t m, const uint32_t* dkey, con
     GS_HIP(gs::launch_composite(ca, h->opt.mode, sc, kernel_event(h, 2), kernel_event(h, 3)));
     if (h->feat_out)  // (feature frames, as in the bin-first tail)
         GS_HIP(gs::launch_composite_features(ca, h->feat_in, h->feat_out, h->feat_k, h->opt.mode, sc));
+    if (h->contrib_on && m > 0) GS_HIP(gs::launch_composite_contrib(ca, h->contrib, h->opt.mode, sc));
     if (slab_t) {
         h->slab_ca = ca;
         h->slab_lists = true;
@@ -1345,6 +1356,12 @@ void fill_stats(gs_handle* h, uint64_t P, const gs::FrameUniforms& U) {
         const int64_t K = h->feat_k, passes = (K + 3) / 4;
         h->stats_fixed_bytes += passes * 4 * T * 8 + 4 * K * (int64_t)U.width * U.height;
         h->stats_rec_bytes += passes * (4 + 48) + 4 * K;
+    }
+    // (a contrib frame: its pass reads the range words and the fetched records again, and the
+    // mask where there is one; the scatter's atomics are not counted)
+    if (h->contrib_on) {
+        h->stats_fixed_bytes += 4 * T * 8 + (h->contrib.mask ? (int64_t)U.width * U.height : 0);
+        h->stats_rec_bytes += 4 + 48;
     }
     s.bytes_composite = h->stats_fixed_bytes + 4 * Pi * h->stats_rec_bytes;
     s.records_fetched = -1;
@@ -1612,9 +1629,20 @@ struct FeatureCall {
     int32_t channels;
     float* out;             // [H][W][channels]
 };
+// con (gs_render_contrib; fp32 RGBA frames): also the per-splat blend weight
+// totals of the frame, from one pass behind the colour composite (DESIGN.md
+// §2.13); its buffers are the caller's kind (out_is_device).
+struct ContribCall {
+    const uint8_t* mask;  // [H][W] or null
+    uint64_t* sum;        // [n]
+    uint32_t* count;      // [n]
+    uint32_t* max;        // [n]
+    bool accumulate;
+};
 static gs_status render_frame(gs_handle* h, const float* view, const float* proj, int32_t W, int32_t H,
                               void* out_user, int32_t out_is_device, bool bgra8, void* stream, bool band = false,
-                              float* depth_user = nullptr, const FeatureCall* feat = nullptr) {
+                              float* depth_user = nullptr, const FeatureCall* feat = nullptr,
+                              const ContribCall* con = nullptr) {
     gs_status s = check_ready(h);
     if (s != GS_OK) return s;
     if (!view || !proj || !out_user || W <= 0 || H <= 0 || W > 65535 || H > 65535)
@@ -1624,6 +1652,9 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
     if (feat && (h->opt.cap > 0 || h->opt.mode == GS_MODE_MLAB))  // (before anything is queued)
         return fail(GS_ERR_UNSUPPORTED, "gs_render_features: tile and live50 modes without a fragment cap only");
     if (feat && h->world != 1) return fail(GS_ERR_UNSUPPORTED, "gs_render_features: single-GPU handles only");
+    if (con && (h->opt.cap > 0 || h->opt.mode == GS_MODE_MLAB))  // (before anything is queued)
+        return fail(GS_ERR_UNSUPPORTED, "gs_render_contrib: tile and live50 modes without a fragment cap only");
+    if (con && h->world != 1) return fail(GS_ERR_UNSUPPORTED, "gs_render_contrib: single-GPU handles only");
     // (the depth and feature images of this frame only: cleared again on every way out)
     struct DepthScope {
         gs_handle* h;
@@ -1632,12 +1663,16 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
             h->feat_in = nullptr;
             h->feat_out = nullptr;
             h->feat_k = 0;
+            h->contrib = gs::ContribArgs{};
+            h->contrib_on = false;
         }
     } depth_scope{h};
     h->depth_out = nullptr;
     h->feat_in = nullptr;
     h->feat_out = nullptr;
     h->feat_k = 0;
+    h->contrib = gs::ContribArgs{};
+    h->contrib_on = false;
     hipStream_t st = static_cast<hipStream_t>(stream);
     gs::FrameUniforms U = make_uniforms(view, proj, W, H);
     const uint32_t T = (uint32_t)(U.tiles_x * U.tiles_y);
@@ -1696,6 +1731,36 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
             h->feat_out = h->fbf.as<float>();
         }
     }
+    const size_t cn = (size_t)h->n;
+    if (con) {
+        h->contrib_on = true;
+        h->contrib.mask = con->mask;
+        h->contrib.sum = reinterpret_cast<unsigned long long*>(con->sum);
+        h->contrib.count = con->count;
+        h->contrib.max = con->max;
+        if (!out_is_device) {
+            // (host calls sync before they return, so the staging copies are free here; the
+            // frame's own totals are built from zero, an accumulating call combines on the host)
+            GS_HIP(h->csum.reserve(std::max<size_t>(cn * 8, 16)));
+            GS_HIP(h->ccount.reserve(std::max<size_t>(cn * 4, 16)));
+            GS_HIP(h->cmax.reserve(std::max<size_t>(cn * 4, 16)));
+            h->contrib.sum = h->csum.as<unsigned long long>();
+            h->contrib.count = h->ccount.as<uint32_t>();
+            h->contrib.max = h->cmax.as<uint32_t>();
+            if (con->mask) {
+                GS_HIP(h->cmask.reserve((size_t)W * H));
+                GS_HIP(hipMemcpyAsync(h->cmask.ptr, con->mask, (size_t)W * H, hipMemcpyHostToDevice, st));
+                h->contrib.mask = h->cmask.as<uint8_t>();
+            }
+        }
+        // (the pass adds into the arrays: cleared here on the caller's stream, which is the
+        // composite's also with two frames in flight, so the clears precede the pass)
+        if (cn && (!con->accumulate || !out_is_device)) {
+            GS_HIP(hipMemsetAsync(h->contrib.sum, 0, cn * 8, st));
+            GS_HIP(hipMemsetAsync(h->contrib.count, 0, cn * 4, st));
+            GS_HIP(hipMemsetAsync(h->contrib.max, 0, cn * 4, st));
+        }
+    }
     std::memset(&h->stats, 0, sizeof h->stats);
     h->shard_frame = false;
     // frames_in_flight 2: projection .. binning on the side stream, into the
@@ -1735,9 +1800,9 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
     h->fused_prep = gs_handle::ListPrep{};
     h->order_pick = -1;
     const bool whole = band ? h->band_local : h->world == 1;  // (the binning owns every row it sees)
-    // (a feature frame is a whole-list frame whatever depth_split says: its passes read the
+    // (a feature or contrib frame is a whole-list frame whatever depth_split says: its passes read the
     // whole lists, and the set's cut tables are invalidated as by any uncut frame)
-    const bool cut_on = depth_cuts_on(h) && whole && cut_rule(h, U) && !h->feat_out;
+    const bool cut_on = depth_cuts_on(h) && whole && cut_rule(h, U) && !h->feat_out && !h->contrib_on;
     bool cut_frame = false;
     if (whole && h->n > 0 && h->opt.mode != GS_MODE_MLAB) {
         const bool bf = bin_first_order(h, U, (uint32_t)h->n, h->band_local ? band_nrows : -1, cut_on);
@@ -1807,7 +1872,31 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
         if (depth_user)
             GS_HIP(hipMemcpyAsync(depth_user, h->depth_out, (size_t)W * H * 4, hipMemcpyDeviceToHost, st));
         if (feat) GS_HIP(hipMemcpyAsync(feat->out, h->feat_out, feat_bytes, hipMemcpyDeviceToHost, st));
+        std::vector<uint64_t> fsum;
+        std::vector<uint32_t> fcm;  // (count, then max)
+        if (con && cn) {
+            // (an accumulating call: the frame's totals come down beside the caller's arrays)
+            uint64_t* ds = con->sum;
+            uint32_t *dc = con->count, *dm = con->max;
+            if (con->accumulate) {
+                fsum.resize(cn);
+                fcm.resize(2 * cn);
+                ds = fsum.data();
+                dc = fcm.data();
+                dm = fcm.data() + cn;
+            }
+            GS_HIP(hipMemcpyAsync(ds, h->contrib.sum, cn * 8, hipMemcpyDeviceToHost, st));
+            GS_HIP(hipMemcpyAsync(dc, h->contrib.count, cn * 4, hipMemcpyDeviceToHost, st));
+            GS_HIP(hipMemcpyAsync(dm, h->contrib.max, cn * 4, hipMemcpyDeviceToHost, st));
+        }
         GS_HIP(hipStreamSynchronize(st));
+        if (con && cn && con->accumulate) {
+            for (size_t i = 0; i < cn; ++i) {
+                con->sum[i] += fsum[i];
+                con->count[i] += fcm[i];
+                con->max[i] = std::max(con->max[i], fcm[cn + i]);
+            }
+        }
     }
     fill_stats(h, P, U);
     if (bgra8) {
@@ -1845,6 +1934,21 @@ gs_status gs_render_features(gs_handle* h, const float* view, const float* proj,
     if (!features && h->n > 0) return fail(GS_ERR_INVALID_ARG, "gs_render_features: null features");
     const FeatureCall fc{features, channels, out_features};
     return render_frame(h, view, proj, W, H, out_rgba, is_device, false, stream, false, nullptr, &fc);
+}
+
+gs_status gs_render_contrib(gs_handle* h, const float* view, const float* proj, int32_t W, int32_t H,
+                            const uint8_t* mask, float* out_rgba, uint64_t* out_sum, uint32_t* out_count,
+                            uint32_t* out_max, int32_t accumulate, int32_t is_device, void* stream) {
+    // (the arguments are judged first, also on a handle that was never initialised)
+    if (!h) return fail(GS_ERR_INVALID_ARG, "gs_render_contrib: null handle");
+    if (!view || !proj || !out_rgba || W <= 0 || H <= 0 || W > 65535 || H > 65535)
+        return fail(GS_ERR_INVALID_ARG, "gs_render_contrib: bad arguments");
+    if (accumulate < 0 || accumulate > 1 || is_device < 0 || is_device > 1)
+        return fail(GS_ERR_INVALID_ARG, "gs_render_contrib: accumulate and is_device must be 0 or 1");
+    if ((!out_sum || !out_count || !out_max) && h->n > 0)
+        return fail(GS_ERR_INVALID_ARG, "gs_render_contrib: null output array");
+    const ContribCall cc{mask, out_sum, out_count, out_max, accumulate != 0};
+    return render_frame(h, view, proj, W, H, out_rgba, is_device, false, stream, false, nullptr, nullptr, &cc);
 }
 
 gs_status gs_render_bgra8(gs_handle* h, const float* view, const float* proj, int32_t W, int32_t H,

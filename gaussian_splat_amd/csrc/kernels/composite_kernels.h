@@ -1,5 +1,5 @@
 // composite_kernels.h — the composite kernels' bodies, written once, and the
-// "values" policies that tell colour, depth and feature frames apart.
+// "values" policies that tell colour, depth, feature and contrib frames apart.
 //
 // composite_tile_body (one 16x16 tile per workgroup) and composite_strip_body (two tiles
 // per workgroup, two pixels per lane) are the bodies of every composite kernel:
@@ -10,9 +10,11 @@
 // composite_strip_kernel (composite.hip, colour), composite_depth_kernel and
 // composite_strip_depth_kernel (composite_depth.hip, gs_render_depth, DESIGN.md
 // §2.11), composite_feat_kernel and composite_strip_feat_kernel
-// (composite_features.hip, gs_render_features, §2.12).
+// (composite_features.hip, gs_render_features, §2.12), composite_contrib_kernel
+// and composite_strip_contrib_kernel (composite_contrib.hip, gs_render_contrib,
+// §2.13).
 //
-// Everything that differs between the three is stated in a policy V, what a
+// Everything that differs between them is stated in a policy V, what a
 // frame kind composites per pixel beside T:
 //   Own, gather   what the record's owner lane loads beside its rc[] chunks,
 //                 with them (in flight while the batch before is composited)
@@ -29,6 +31,11 @@
 //   store         (kFourth) a finished pixel (px, row) of the output: o = (the
 //                 three first accumulators, alpha), d the fourth accumulator;
 //                 without a fourth value the bodies' own colour epilogues run
+//   kContrib      the transposed pass (ContribValues, gs_render_contrib, §2.13;
+//                 composite_contrib_kernel and composite_strip_contrib_kernel,
+//                 composite_contrib.hip): no pixel is stored; scale, weight and
+//                 scatter turn each fragment's blend weight into its splat's
+//                 totals
 #pragma once
 
 #include <hip/hip_ext.h>
@@ -44,7 +51,7 @@ namespace gs {
 // and MLAB frames are colour frames: their epilogues are the kernel's modes.)
 struct ColourValues {
     struct Own {};
-    static constexpr bool kFourth = false, kWholeFrame = false;
+    static constexpr bool kFourth = false, kWholeFrame = false, kContrib = false;
     static constexpr int kWaves = 8;
     __device__ __forceinline__ Own gather(const CompositeArgs&, uint32_t) const { return {}; }
     __device__ __forceinline__ float4 values(const Own&, float r, float g, float b) const {
@@ -60,7 +67,7 @@ struct ColourValues {
 // frame time: profiles/depth/ab_depth_waves.txt; 8 spills).
 struct DepthValues {
     using Own = float;
-    static constexpr bool kFourth = true, kWholeFrame = false;
+    static constexpr bool kFourth = true, kWholeFrame = false, kContrib = false;
     static constexpr int kWaves = 6;
     __device__ __forceinline__ Own gather(const CompositeArgs& a, uint32_t id) const { return a.zf[id]; }
     __device__ __forceinline__ float4 values(const Own& zf, float r, float g, float b) const {
@@ -86,7 +93,7 @@ struct DepthValues {
 template <bool VIN, bool VOUT>
 struct FeatureValues {
     using Own = float4;
-    static constexpr bool kFourth = true, kWholeFrame = true;
+    static constexpr bool kFourth = true, kWholeFrame = true, kContrib = false;
     static constexpr int kWaves = 6;
     FeatureArgs f;
     // channels of this launch that exist (1..4; 4 with VIN / VOUT)
@@ -118,6 +125,56 @@ struct FeatureValues {
             if (n > 1u) p[1] = o.y;
             if (n > 2u) p[2] = o.z;
             if (n > 3u) p[3] = d;
+        }
+    }
+};
+
+// Contrib frames (gs_render_contrib): the transposed pass.
+// T per pixel and nothing else: no colour is accumulated and no pixel is
+// written (kContrib drops the stores, so the bodies' accumulators are dead).
+// Per record and pixel the blend weight w the colour frame multiplies the
+// splat's colour with (tile rule: alpha T; live50 rule: T) is quantised,
+//   q(w) = (uint32_t)(min(max(w, 0), 1) * 2^24)   (truncation; NaN -> 0),
+// so every total is an integer whatever the order of summation.  The scale is
+// the pixel's own (scale()): 2^24, or 0 for a pixel the caller's mask leaves
+// out, which then composites as always and contributes nothing.
+//  - the record's splat id travels where a colour frame stages r: the owner
+//    lane holds it (gather), values() puts its bits into the first value;
+//  - weight() is the hook inside the exec-masked update; scatter() runs after
+//    it with every lane of the wave active, q = 0 in the lanes that skipped
+//    the update: count = popcount(ballot(q > 0)), sum and max by a 6-step DPP
+//    reduction (a wave's sum is at most 128 * 2^24 = 2^31), then one lane issues
+//    the three atomics of the (record, wave); nothing when no lane has q > 0.
+struct ContribValues {
+    using Own = uint32_t;
+    static constexpr bool kFourth = false, kWholeFrame = true, kContrib = true;
+    static constexpr int kWaves = 8;
+    ContribArgs k;
+    __device__ __forceinline__ Own gather(const CompositeArgs&, uint32_t id) const { return id; }
+    __device__ __forceinline__ float4 values(const Own& id, float, float, float) const {
+        return make_float4(__uint_as_float(id), 0.0f, 0.0f, 0.0f);
+    }
+    __device__ __forceinline__ float scale(bool inside, size_t pix) const {
+        return inside && (!k.mask || k.mask[pix] != 0) ? 16777216.0f : 0.0f;
+    }
+    __device__ __forceinline__ uint32_t weight(float w, float scale) const {
+        return (uint32_t)(fminf(fmaxf(w, 0.0f), 1.0f) * scale);
+    }
+    // qs: the lane's quantised weights summed (one pixel, or the strip kernel's
+    // two), qm: their max, cnt: the wave's pixels with q > 0 (scalar)
+    __device__ __forceinline__ void scatter(float id_bits, uint32_t qs, uint32_t qm, uint32_t cnt) const {
+        if (cnt == 0u) return;  // (wave-uniform)
+        // (the scans' last lane holds the totals and issues the atomics.  The id passes
+        // through an identity DPP move, quad_perm [0, 1, 2, 3], which the compiler takes
+        // for a per-lane value: with an address it knows to be wave-uniform its atomic
+        // optimiser wraps each of the three atomics in a lane election, a reduction over
+        // the active lanes and a branch of its own, all for the one lane that is active)
+        const uint32_t s = wave_scan_dpp<false>(qs), m = wave_scan_dpp<true>(qm);
+        const uint32_t id = (uint32_t)__builtin_amdgcn_mov_dpp((int)__float_as_uint(id_bits), 0xE4, 0xf, 0xf, true);
+        if (lane_id() == 63u) {
+            (void)atomicAdd(k.sum + id, (unsigned long long)s);
+            (void)atomicAdd(k.count + id, cnt);
+            (void)atomicMax(k.max + id, m);
         }
     }
 };
@@ -314,6 +371,8 @@ __device__ __forceinline__ void composite_tile_body(const CompositeArgs a, uint3
     // compact = owned bin rows stacked (multi-GPU band buffer)
     const int orow = !V::kWholeFrame && a.compact ? owned_row * kBin + (py - by * kBin) : py;
     const size_t pix = (size_t)py * width + px;
+    float qscale = 0.0f;  // (V::kContrib) the pixel's weight scale, 0 where the mask leaves it out
+    if constexpr (V::kContrib) qscale = v.scale(inside, pix);
     // PASS 2: this quadrant was left open by the front list (else its pixels
     // start finished, and were written already)
     const bool resumed = PASS == 2 && (wave == 0 ? oq.x : wave == 1 ? oq.y : wave == 2 ? oq.z : oq.w) != 0u;
@@ -360,9 +419,9 @@ __device__ __forceinline__ void composite_tile_body(const CompositeArgs a, uint3
     // gaussian's exec-masked block.
     auto body_v = [&](const float4 aa, const float4 bb, const float2 cc, uint32_t id, _Float16 hd, float dd) {
         const float u = __builtin_fmaf(aa.z, lx, __builtin_fmaf(aa.w, ly, aa.x));
-        const float v = __builtin_fmaf(bb.x, lx, __builtin_fmaf(bb.y, ly, aa.y));
-        const float qq = __builtin_fmaf(v, v, u * u);
-        const bool covered = fmaxf(fabsf(u), fabsf(v)) <= kBoxS && qq <= kQMaxS;
+        const float vv = __builtin_fmaf(bb.x, lx, __builtin_fmaf(bb.y, ly, aa.y));
+        const float qq = __builtin_fmaf(vv, vv, u * u);
+        const bool covered = fmaxf(fabsf(u), fabsf(vv)) <= kBoxS && qq <= kQMaxS;
         if constexpr (MODE == 2) {
             // arrival order: the a.cap-th covering fragment fixes the threshold
             const bool in = !done && covered;
@@ -376,16 +435,19 @@ __device__ __forceinline__ void composite_tile_body(const CompositeArgs a, uint3
         } else {
             bool in = !finished() && covered;
             if constexpr (CAP) in = in && id <= thr;
+            uint32_t q = 0u;  // (V::kContrib) the fragment's quantised weight
             if (in) {
                 const float alpha = bb.z * gs_gauss2(qq);
                 if constexpr (MODE == 0) {
                     const float sa = alpha * T;
+                    if constexpr (V::kContrib) q = v.weight(sa, qscale);
                     C0 = __builtin_fmaf(bb.w, sa, C0);
                     C1 = __builtin_fmaf(cc.x, sa, C1);
                     C2 = __builtin_fmaf(cc.y, sa, C2);
                     if constexpr (V::kFourth) D = __builtin_fmaf(dd, sa, D);
                     T = T - sa;
                 } else {
+                    if constexpr (V::kContrib) q = v.weight(T, qscale);
                     C0 = __builtin_fmaf(bb.w, T, C0);
                     C1 = __builtin_fmaf(cc.x, T, C1);
                     C2 = __builtin_fmaf(cc.y, T, C2);
@@ -393,6 +455,8 @@ __device__ __forceinline__ void composite_tile_body(const CompositeArgs a, uint3
                     T = T * (1.0f - alpha);
                 }
             }
+            // (every lane again: the record's id is the first staged value)
+            if constexpr (V::kContrib) v.scatter(bb.w, q, q, (uint32_t)__popcll(__ballot(q != 0u)));
         }
     };
     // a record's c words: (g, b), the id where the body needs it, and the
@@ -569,7 +633,8 @@ __device__ __forceinline__ void composite_tile_body(const CompositeArgs a, uint3
         open_w = __ballot(!finished()) != 0;
         keep = open_w && trunc;
     }
-    const bool write = inside && (PASS != 2 || resumed);  // (PASS 2: the rest was written by pass 1)
+    // (V::kContrib: the pass writes no pixel)
+    const bool write = !V::kContrib && inside && (PASS != 2 || resumed);  // (PASS 2: the rest was written by pass 1)
     if (write) {
         if (keep) {
             a.state[pix] = make_float4(C0, C1, C2, T);  // (C, T) and D
@@ -703,6 +768,11 @@ __device__ __forceinline__ void composite_strip_body(const CompositeArgs a, uint
     constexpr int kAcc = V::kFourth ? 4 : 3;
     float A[kAcc] = {}, B[kAcc] = {};
     const size_t pixA = (size_t)py * width + pxA, pixB = pixA + 8;
+    float qsA = 0.0f, qsB = 0.0f;  // (V::kContrib) the pixels' weight scales, 0 where the mask leaves one out
+    if constexpr (V::kContrib) {
+        qsA = v.scale(inA, pixA);
+        qsB = v.scale(inB, pixB);
+    }
     if constexpr (PASS == 2) {
         TA = 0.0f;
         TB = 0.0f;
@@ -727,9 +797,9 @@ __device__ __forceinline__ void composite_strip_body(const CompositeArgs a, uint
     auto pixel = [&](float lx, float tu, float tv, const float4& aa, const float4& bb, float dd, float& T,
                      float (&C)[kAcc]) {
         const float u = __builtin_fmaf(aa.x, lx, tu);
-        const float v = __builtin_fmaf(aa.z, lx, tv);
-        const float qq = __builtin_fmaf(v, v, u * u);
-        const bool covered = fmaxf(fabsf(u), fabsf(v)) <= kBoxS && qq <= kQMaxS;
+        const float vv = __builtin_fmaf(aa.z, lx, tv);
+        const float qq = __builtin_fmaf(vv, vv, u * u);
+        const bool covered = fmaxf(fabsf(u), fabsf(vv)) <= kBoxS && qq <= kQMaxS;
         if (!fin(T) && covered) {
             const float alpha = bb.x * gs_gauss2(qq);
             const float val[4] = {bb.y, bb.z, bb.w, dd};
@@ -745,13 +815,50 @@ __device__ __forceinline__ void composite_strip_body(const CompositeArgs a, uint
             }
         }
     };
+    // (V::kContrib) the same pixel and record without accumulators: coverage,
+    // alpha and T op for op, and the fragment's quantised weight (qs: the
+    // pixel's weight scale) where pixel() has its fmas, 0 where it skips.  A
+    // route of its own: as a hook inside pixel(), behind `if constexpr`, the
+    // extra parameters moved the colour strip kernels' instruction streams
+    // (profiles/contrib/instr_compare.txt).
+    auto pixel_w = [&](float lx, float tu, float tv, const float4& aa, const float4& bb, float& T,
+                       float qs) -> uint32_t {
+        const float u = __builtin_fmaf(aa.x, lx, tu);
+        const float vv = __builtin_fmaf(aa.z, lx, tv);
+        const float qq = __builtin_fmaf(vv, vv, u * u);
+        const bool covered = fmaxf(fabsf(u), fabsf(vv)) <= kBoxS && qq <= kQMaxS;
+        uint32_t q = 0u;
+        if constexpr (V::kContrib) {
+            if (!fin(T) && covered) {
+                const float alpha = bb.x * gs_gauss2(qq);
+                if constexpr (MODE == 0) {
+                    const float sa = alpha * T;
+                    q = v.weight(sa, qs);
+                    T = T - sa;
+                } else {
+                    q = v.weight(T, qs);
+                    T = T * (1.0f - alpha);
+                }
+            }
+        }
+        return q;
+    };
     // a record for both of the wave's quadrants; sel (scalar): bit 0 quadrant
     // A may be reached, bit 1 quadrant B; dd its fourth value
     auto body = [&](const float4& aa, const float4& bb, const float2& cc, float dd, uint32_t sel) {
         const float tu = __builtin_fmaf(aa.y, ly, cc.x);  // fma(-A'y, ly, U0)
         const float tv = __builtin_fmaf(aa.w, ly, cc.y);  // fma(-B'y, ly, V0)
-        if (sel & 1u) pixel(lxA, tu, tv, aa, bb, dd, TA, A);
-        if (sel & 2u) pixel(lxB, tu, tv, aa, bb, dd, TB, B);
+        if constexpr (V::kContrib) {
+            uint32_t qA = 0u, qB = 0u;
+            if (sel & 1u) qA = pixel_w(lxA, tu, tv, aa, bb, TA, qsA);
+            if (sel & 2u) qB = pixel_w(lxB, tu, tv, aa, bb, TB, qsB);
+            // (every lane again: the record's id is the first staged value)
+            v.scatter(bb.y, qA + qB, qA > qB ? qA : qB,
+                      (uint32_t)__popcll(__ballot(qA != 0u)) + (uint32_t)__popcll(__ballot(qB != 0u)));
+        } else {
+            if (sel & 1u) pixel(lxA, tu, tv, aa, bb, dd, TA, A);
+            if (sel & 2u) pixel(lxB, tu, tv, aa, bb, dd, TB, B);
+        }
     };
 
     // Gathers as composite_kernel: wave w loads records 64w..64w+63 of a
@@ -971,8 +1078,10 @@ __device__ __forceinline__ void composite_strip_body(const CompositeArgs a, uint
             a.out[(size_t)orow * width + px] = make_float4(C0, C1, C2, 1.0f - T);
         }
     };
-    store(resA, keepA, qx, A[0], A[1], A[2], TA, A[kAcc - 1]);  // (C3: the fourth accumulator where one exists)
-    store(resB, keepB, qx + 8, B[0], B[1], B[2], TB, B[kAcc - 1]);
+    if constexpr (!V::kContrib) {  // (a contrib pass writes no pixel)
+        store(resA, keepA, qx, A[0], A[1], A[2], TA, A[kAcc - 1]);  // (C3: the fourth accumulator where one exists)
+        store(resB, keepB, qx + 8, B[0], B[1], B[2], TB, B[kAcc - 1]);
+    }
     if constexpr (PASS == 1) {
         if (lane == 0) {
             qr[qA] = openA ? 0xFFFFFFFFu : wendA;

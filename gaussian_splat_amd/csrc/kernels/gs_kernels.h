@@ -351,6 +351,23 @@ struct FeatureArgs {
 // stores.  Rows of splats in no list are never read.
 hipError_t launch_composite_features(const CompositeArgs& a, const float* feat, float* out, int channels, int mode,
                                      hipStream_t st);
+// Contrib frames (gs_render_contrib; composite_contrib.hip):
+// the second parameter of the contrib composites, beside CompositeArgs.
+struct ContribArgs {
+    const uint8_t* mask;      // [height][width], a pixel counts where mask != 0 (null: every pixel)
+    unsigned long long* sum;  // [n] += the splat's quantised blend weights over the counted pixels
+    uint32_t* count;          // [n] += the counted pixels with a quantised weight > 0
+    uint32_t* max;            // [n]  = max with the largest quantised weight
+};
+// One pass over the whole lists a (as launch_composite_features: pass 0, every
+// bin row, tile / live50 rules, no cap) the frame's colour composite has just
+// read, on its stream: T per pixel, no colour, no pixel written; per record
+// and wave the quantised weights q(w) = (uint32_t)(min(max(w, 0), 1) * 2^24)
+// of its pixels (w = alpha T, tile rule; T, live50 rule) are reduced in the
+// wave and one lane adds them to the splat's entries with three atomics.  The
+// arrays are combined into, never cleared: the caller zeroes them first for a
+// frame's own totals.
+hipError_t launch_composite_contrib(const CompositeArgs& a, const ContribArgs& k, int mode, hipStream_t st);
 // One 256-lane workgroup per owned 16x16 tile.  mode 0 = tile rule (A >= 0.99
 // break), 1 = live50 rule (T < 0.01 break), 2 = MLAB k-buffer (a.vals
 // index-ordered, a.dkey set, no cap); with a.cap > 0 only fragments with

@@ -238,6 +238,46 @@ gs_status gs_render_depth(gs_handle *h, const float view[16], const float proj[1
 gs_status gs_render_features(gs_handle *h, const float view[16], const float proj[16], int32_t width,
                              int32_t height, const float *features, int32_t channels, float *out_rgba,
                              float *out_features, int32_t is_device, void *hip_stream);
+/* Colour frame as gs_render, plus what each splat puts into it: the transposed
+ * question to the three calls above.  For splat i of the loaded (post-crop)
+ * scene, in gs_get_scene's order, and pixel p, let w(i,p) be the factor that
+ * multiplies the splat's colour at p in this frame's composite (tile rule:
+ * alpha * T, the fp32 product as the kernel forms it; live50 rule: T before
+ * the fragment); it exists only where the fragment is composited.  Weights are
+ * quantised, q(w) = (uint32_t)(fminf(fmaxf(w, 0), 1) * 16777216.0f)
+ * (truncation; 0 .. 2^24; NaN gives 0), so every total is an integer and does
+ * not depend on the order of summation.  Over the pixels with mask[p] != 0
+ * (mask: width*height bytes, row-major, y down; NULL = every pixel):
+ *   out_sum[i]   = sum of q(w(i,p))           (uint64_t; sum / 2^24 is the
+ *                                              splat's total weight in pixels)
+ *   out_count[i] = pixels with q(w(i,p)) > 0  (uint32_t)
+ *   out_max[i]   = max of q(w(i,p))           (uint32_t)
+ * gs_point_count(h) entries each; splats that reach no list get 0, 0, 0.  A
+ * masked-out pixel composites as always and contributes nothing.
+ * accumulate 0: the three arrays are overwritten, every entry, zeros
+ * included.  accumulate 1: the frame's totals are combined into what the
+ * arrays hold (sum +=, count +=, max = max(...)), entries of splats with no
+ * contribution stay as they were: a score over a set of cameras without a
+ * host round trip.  out_count wraps modulo 2^32 (a splat can add up to
+ * width*height per frame); out_sum cannot overflow in any realistic number of
+ * frames (a frame adds less than 2^56).
+ * is_device covers mask, out_rgba and the three arrays (1: HBM pointers, async
+ * on `hip_stream`, the buffers must not overlap; 0: host pointers, the call
+ * syncs, and an accumulating call combines on the host after the download);
+ * the types' natural alignment is enough.  The arrays may be NULL only for a
+ * scene of 0 splats.  out_rgba is bit-identical to gs_render's, and the four
+ * render calls may alternate freely on one handle.  A contrib frame builds
+ * whole bin lists whatever gs_options.depth_split says (gs_stats.cut_frame ==
+ * 0), so the next colour frames on its buffer set learn their depth cuts
+ * again.
+ * Tile and live50 modes with cap == 0 on a single-GPU handle; cap > 0, MLAB
+ * mode or a sharded handle: GS_ERR_UNSUPPORTED, nothing is enqueued.
+ * accumulate or is_device outside {0, 1}: GS_ERR_INVALID_ARG.
+ * (Added without an ABI version change: an addition.) */
+gs_status gs_render_contrib(gs_handle *h, const float view[16], const float proj[16], int32_t width,
+                            int32_t height, const uint8_t *mask, float *out_rgba, uint64_t *out_sum,
+                            uint32_t *out_count, uint32_t *out_max, int32_t accumulate, int32_t is_device,
+                            void *hip_stream);
 gs_status gs_last_stats(gs_handle *h, gs_stats *out);
 /* stage_timing 2: preprocess and composite kernel times (ms, from the events
  * in their dispatch packets) of the last min(max_frames, 64) frames rendered

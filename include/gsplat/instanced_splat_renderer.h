@@ -55,6 +55,15 @@ public:
                         int channels, const simd_float4x4& viewMatrix, const simd_float4x4& projectionMatrix,
                         float viewportWidth, float viewportHeight);
 
+    // Addition (not in the reference): render() plus each splat's quantised
+    // blend weight totals over the frame (gs_render_contrib): sum, count and
+    // max are getPointCount()-entry arrays in HBM, mask (may be null) the
+    // width*height byte image in HBM of the pixels that count; accumulate
+    // combines the frame's totals into what the arrays hold.
+    void renderContrib(void* commandBuffer, void* drawableTexture, const uint8_t* mask, uint64_t* sum,
+                       uint32_t* count, uint32_t* max, bool accumulate, const simd_float4x4& viewMatrix,
+                       const simd_float4x4& projectionMatrix, float viewportWidth, float viewportHeight);
+
     // Additions (not in the reference): status of the last call, frame stats.
     gs_status lastStatus() const { return status_; }
     gs_stats lastStats() const;
