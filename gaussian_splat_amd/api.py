@@ -29,6 +29,8 @@ RECORD_DTYPE = np.dtype([("cx", "<f4"), ("cy", "<f4"), ("ax", "<f4"), ("ay", "<f
 MODES = {"tile": 0, "live50": 1, "mlab": 2}
 BINNING = {"default": 0, "depth_first": 1, "bin_first": 2}  # gs_binning
 MAX_FEATURE_CHANNELS = 64  # GS_MAX_FEATURE_CHANNELS (gs_render_features)
+MAX_ID_SLOTS = 4  # GS_MAX_ID_SLOTS (gs_render_ids)
+ID_NONE = 0xFFFFFFFF  # GS_ID_NONE: an empty slot of gs_render_ids
 
 
 def _mat16(m) -> C.Array:
@@ -491,6 +493,84 @@ class InstancedSplatRenderer:
                                       max.ctypes.data if n else None, 1 if accumulate else 0, 0, None),
               "gs_render_contrib")
         return out, sum, count, max
+
+    def render_ids(self, view, proj, width: int, height: int, slots: int = 4, out=None, ids=None, q=None, count=None,
+                   want_q: bool = True, want_count: bool = True, stream=None):
+        """Render colour and each pixel's top `slots` splats by blend weight
+        (gs_render_ids): returns (rgba, ids, q, count), CUDA tensors (H, W, 4)
+        float32 and (H, W, slots), (H, W, slots), (H, W) torch.int32 holding the
+        uint32 bits.  The candidates of a pixel are the fragments the frame
+        composites there with q > 0, q = 0 .. 2**24 being render_contrib's quantised
+        weight; they are ordered by q descending, then splat index ascending.
+        ids[y, x, k] is the k-th candidate's index into the loaded scene
+        (get_scene's order), q[y, x, k] its weight, count[y, x] the number of
+        candidates (it may exceed slots).  Empty slots hold ID_NONE (-1 as int32)
+        and q = 0; every element is written, also where nothing lands.
+        want_q=False / want_count=False leave that output out (None is returned in
+        its place).  `rgba` is render()'s frame bit for bit.  Tile and live50 modes
+        without a fragment cap; the frame builds whole bin lists whatever
+        depth_split says."""
+        import torch
+
+        slots = int(slots)
+        if not 1 <= slots <= MAX_ID_SLOTS:
+            raise ValueError(f"slots must be 1..{MAX_ID_SLOTS}, got {slots}")
+        dev = torch.device(f"cuda:{self.device or 0}")
+
+        def arr(t, name, numel):
+            if t is None:  # (allocated once every argument is judged)
+                return None
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be a torch tensor")
+            if t.dtype != torch.int32:
+                raise ValueError(f"{name} must be torch.int32, got {t.dtype}")
+            if t.numel() != numel:
+                raise ValueError(f"{name} must have {numel} elements, got {t.numel()}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            if not t.is_cuda or t.device != dev:
+                raise ValueError(f"{name} must be on the handle's device {dev}, got {t.device}")
+            return t
+
+        px = int(width) * int(height)
+        ids = arr(ids, "ids", px * slots)
+        q = arr(q, "q", px * slots)
+        count = arr(count, "count", px)
+        if ids is None:
+            ids = torch.empty((height, width, slots), dtype=torch.int32, device=dev)
+        if q is None and want_q:
+            q = torch.empty((height, width, slots), dtype=torch.int32, device=dev)
+        if count is None and want_count:
+            count = torch.empty((height, width), dtype=torch.int32, device=dev)
+        if out is None:
+            out = torch.empty((height, width, 4), dtype=torch.float32, device=dev)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == px * 4
+        assert out.device == dev
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device).cuda_stream
+        check(lib().gs_render_ids(self._h, _mat16(view), _mat16(proj), int(width), int(height), slots,
+                                  C.c_void_p(out.data_ptr()), C.c_void_p(ids.data_ptr()),
+                                  C.c_void_p(q.data_ptr() if q is not None else None),
+                                  C.c_void_p(count.data_ptr() if count is not None else None), 1, C.c_void_p(stream)),
+              "gs_render_ids")
+        return out, ids, q, count
+
+    def render_ids_host(self, view, proj, width: int, height: int, slots: int = 4, want_q: bool = True,
+                        want_count: bool = True):
+        """render_ids into host memory: (rgba (H, W, 4) float32, ids (H, W, slots),
+        q (H, W, slots), count (H, W)) numpy arrays, the last three uint32 (None where
+        not wanted)."""
+        slots = int(slots)
+        if not 1 <= slots <= MAX_ID_SLOTS:
+            raise ValueError(f"slots must be 1..{MAX_ID_SLOTS}, got {slots}")
+        out = np.empty((height, width, 4), np.float32)
+        ids = np.empty((height, width, slots), np.uint32)
+        q = np.empty((height, width, slots), np.uint32) if want_q else None
+        count = np.empty((height, width), np.uint32) if want_count else None
+        check(lib().gs_render_ids(self._h, _mat16(view), _mat16(proj), int(width), int(height), slots, out.ctypes.data,
+                                  ids.ctypes.data, q.ctypes.data if want_q else None,
+                                  count.ctypes.data if want_count else None, 0, None), "gs_render_ids")
+        return out, ids, q, count
 
     def render_bgra8(self, view, proj, width: int, height: int, out=None, stream=None):
         """Render as BGRA8Unorm (the reference's drawable format) into `out`

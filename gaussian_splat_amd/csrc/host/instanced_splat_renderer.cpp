@@ -70,6 +70,16 @@ void InstancedSplatRenderer::renderContrib(void* commandBuffer, void* drawableTe
                                 accumulate ? 1 : 0, 1, commandBuffer);
 }
 
+void InstancedSplatRenderer::renderIds(void* commandBuffer, void* drawableTexture, int slots, uint32_t* ids, uint32_t* q,
+                                       uint32_t* count, const simd_float4x4& viewMatrix,
+                                       const simd_float4x4& projectionMatrix, float viewportWidth,
+                                       float viewportHeight) {
+    if (!handle_ || !drawableTexture || !ids) return;
+    status_ = gs_render_ids(handle_, viewMatrix.data(), projectionMatrix.data(), (int32_t)viewportWidth,
+                            (int32_t)viewportHeight, (int32_t)slots, static_cast<float*>(drawableTexture), ids, q, count, 1,
+                            commandBuffer);
+}
+
 int InstancedSplatRenderer::getPointCount() const { return (int)gs_point_count(handle_); }
 
 gs_stats InstancedSplatRenderer::lastStats() const {

@@ -136,6 +136,13 @@ struct gs_handle {
     gs::ContribArgs contrib{};
     bool contrib_on = false;
     DevBuf cmask, csum, ccount, cmax;
+    // Ids frames (gs_render_ids).  ids: the three device
+    // arrays and the slot count of the frame being enqueued (ids_on false: not
+    // an ids frame), set and cleared by render_frame; iids, iq, icount: their
+    // staging copies for host calls (the call syncs; they only grow).
+    gs::IdArgs ids{};
+    bool ids_on = false;
+    DevBuf iids, iq, icount;
     DevBuf dsk, dso, dsl, dsh, dtk, dto, dtl, dth;  // depth sort: keys, order, rect lo/hi (+ ping-pong)
     DevBuf xmask, xcounts, xtotal;  // multi-GPU exchange
     // depth-slab frames: full-frame ownership; the colour pass
@@ -1067,6 +1074,18 @@ gs_status cut_tail(gs_handle* h, const gs::FrameUniforms& U, gs::CompositeArgs c
     return GS_OK;
 }
 
+// An ids frame's pass behind its colour composite (gs_render_ids, DESIGN.md
+// §2.14).  A scene of 0 splats has no lists to launch over: every pixel is
+// empty, written here.
+static hipError_t ids_pass(gs_handle* h, const gs::CompositeArgs& c, uint32_t m, hipStream_t sc) {
+    if (m > 0) return gs::launch_composite_ids(c, h->ids, h->opt.mode, sc);
+    const size_t px = (size_t)c.width * (size_t)c.height;
+    hipError_t e = hipMemsetAsync(h->ids.ids, 0xFF, px * (size_t)h->ids.slots * 4, sc);
+    if (e == hipSuccess && h->ids.q) e = hipMemsetAsync(h->ids.q, 0, px * (size_t)h->ids.slots * 4, sc);
+    if (e == hipSuccess && h->ids.count) e = hipMemsetAsync(h->ids.count, 0, px * 4, sc);
+    return e;
+}
+
 // Binning + sort + composite over m items (local splats, or received
 // exchange records): depth sort -> bin lists in depth order -> composite.
 // With a fragment cap, per-pixel thresholds come first from index-ordered
@@ -1197,6 +1216,8 @@ gs_status bin_sort_composite(gs_handle* h, uint32_t m, const uint32_t* dkey, con
                 GS_HIP(gs::launch_composite_features(c, h->feat_in, h->feat_out, h->feat_k, h->opt.mode, sc));
             // (contrib frames: the scatter pass, in the same place)
             if (h->contrib_on && m > 0) GS_HIP(gs::launch_composite_contrib(c, h->contrib, h->opt.mode, sc));
+            // (ids frames: the top-K pass, in the same place)
+            if (h->ids_on) GS_HIP(ids_pass(h, c, m, sc));
             if (slab_t) {
                 h->slab_ca = c;
                 h->slab_lists = true;
@@ -1294,6 +1315,7 @@ gs_status bin_sort_composite(gs_handle* h, uint32_t m, const uint32_t* dkey, con
     if (h->feat_out)  // (feature frames, as in the bin-first tail)
         GS_HIP(gs::launch_composite_features(ca, h->feat_in, h->feat_out, h->feat_k, h->opt.mode, sc));
     if (h->contrib_on && m > 0) GS_HIP(gs::launch_composite_contrib(ca, h->contrib, h->opt.mode, sc));
+    if (h->ids_on) GS_HIP(ids_pass(h, ca, m, sc));
     if (slab_t) {
         h->slab_ca = ca;
         h->slab_lists = true;
@@ -1361,6 +1383,13 @@ void fill_stats(gs_handle* h, uint64_t P, const gs::FrameUniforms& U) {
     // mask where there is one; the scatter's atomics are not counted)
     if (h->contrib_on) {
         h->stats_fixed_bytes += 4 * T * 8 + (h->contrib.mask ? (int64_t)U.width * U.height : 0);
+        h->stats_rec_bytes += 4 + 48;
+    }
+    // (an ids frame: its pass reads the range words and the fetched records again, and writes the
+    // slots' ids, their weights and the counts where they are wanted)
+    if (h->ids_on) {
+        const int64_t px = (int64_t)U.width * U.height;
+        h->stats_fixed_bytes += 4 * T * 8 + px * 4 * ((h->ids.q ? 2 : 1) * (int64_t)h->ids.slots + (h->ids.count ? 1 : 0));
         h->stats_rec_bytes += 4 + 48;
     }
     s.bytes_composite = h->stats_fixed_bytes + 4 * Pi * h->stats_rec_bytes;
@@ -1639,10 +1668,19 @@ struct ContribCall {
     uint32_t* max;        // [n]
     bool accumulate;
 };
+// idc (gs_render_ids; fp32 RGBA frames): also each pixel's top `slots` splats
+// by blend weight, from one pass behind the colour composite (DESIGN.md
+// §2.14); its buffers are the caller's kind (out_is_device).
+struct IdCall {
+    uint32_t* ids;    // [H][W][slots]
+    uint32_t* q;      // [H][W][slots] or null
+    uint32_t* count;  // [H][W] or null
+    int32_t slots;
+};
 static gs_status render_frame(gs_handle* h, const float* view, const float* proj, int32_t W, int32_t H,
                               void* out_user, int32_t out_is_device, bool bgra8, void* stream, bool band = false,
                               float* depth_user = nullptr, const FeatureCall* feat = nullptr,
-                              const ContribCall* con = nullptr) {
+                              const ContribCall* con = nullptr, const IdCall* idc = nullptr) {
     gs_status s = check_ready(h);
     if (s != GS_OK) return s;
     if (!view || !proj || !out_user || W <= 0 || H <= 0 || W > 65535 || H > 65535)
@@ -1655,6 +1693,9 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
     if (con && (h->opt.cap > 0 || h->opt.mode == GS_MODE_MLAB))  // (before anything is queued)
         return fail(GS_ERR_UNSUPPORTED, "gs_render_contrib: tile and live50 modes without a fragment cap only");
     if (con && h->world != 1) return fail(GS_ERR_UNSUPPORTED, "gs_render_contrib: single-GPU handles only");
+    if (idc && (h->opt.cap > 0 || h->opt.mode == GS_MODE_MLAB))  // (before anything is queued)
+        return fail(GS_ERR_UNSUPPORTED, "gs_render_ids: tile and live50 modes without a fragment cap only");
+    if (idc && h->world != 1) return fail(GS_ERR_UNSUPPORTED, "gs_render_ids: single-GPU handles only");
     // (the depth and feature images of this frame only: cleared again on every way out)
     struct DepthScope {
         gs_handle* h;
@@ -1665,6 +1706,8 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
             h->feat_k = 0;
             h->contrib = gs::ContribArgs{};
             h->contrib_on = false;
+            h->ids = gs::IdArgs{};
+            h->ids_on = false;
         }
     } depth_scope{h};
     h->depth_out = nullptr;
@@ -1673,6 +1716,8 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
     h->feat_k = 0;
     h->contrib = gs::ContribArgs{};
     h->contrib_on = false;
+    h->ids = gs::IdArgs{};
+    h->ids_on = false;
     hipStream_t st = static_cast<hipStream_t>(stream);
     gs::FrameUniforms U = make_uniforms(view, proj, W, H);
     const uint32_t T = (uint32_t)(U.tiles_x * U.tiles_y);
@@ -1761,6 +1806,23 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
             GS_HIP(hipMemsetAsync(h->contrib.max, 0, cn * 4, st));
         }
     }
+    const size_t id_px = (size_t)W * H;
+    if (idc) {
+        h->ids_on = true;
+        h->ids = gs::IdArgs{idc->ids, idc->q, idc->count, idc->slots, 0};
+        if (!out_is_device) {  // (host calls sync before they return: one staging copy of each serves every frame)
+            GS_HIP(h->iids.reserve(id_px * (size_t)idc->slots * 4));
+            h->ids.ids = h->iids.as<uint32_t>();
+            if (idc->q) {
+                GS_HIP(h->iq.reserve(id_px * (size_t)idc->slots * 4));
+                h->ids.q = h->iq.as<uint32_t>();
+            }
+            if (idc->count) {
+                GS_HIP(h->icount.reserve(id_px * 4));
+                h->ids.count = h->icount.as<uint32_t>();
+            }
+        }
+    }
     std::memset(&h->stats, 0, sizeof h->stats);
     h->shard_frame = false;
     // frames_in_flight 2: projection .. binning on the side stream, into the
@@ -1800,9 +1862,9 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
     h->fused_prep = gs_handle::ListPrep{};
     h->order_pick = -1;
     const bool whole = band ? h->band_local : h->world == 1;  // (the binning owns every row it sees)
-    // (a feature or contrib frame is a whole-list frame whatever depth_split says: its passes read the
-    // whole lists, and the set's cut tables are invalidated as by any uncut frame)
-    const bool cut_on = depth_cuts_on(h) && whole && cut_rule(h, U) && !h->feat_out && !h->contrib_on;
+    // (a feature, contrib or ids frame is a whole-list frame whatever depth_split says: its passes read
+    // the whole lists, and the set's cut tables are invalidated as by any uncut frame)
+    const bool cut_on = depth_cuts_on(h) && whole && cut_rule(h, U) && !h->feat_out && !h->contrib_on && !h->ids_on;
     bool cut_frame = false;
     if (whole && h->n > 0 && h->opt.mode != GS_MODE_MLAB) {
         const bool bf = bin_first_order(h, U, (uint32_t)h->n, h->band_local ? band_nrows : -1, cut_on);
@@ -1889,6 +1951,12 @@ static gs_status render_frame(gs_handle* h, const float* view, const float* proj
             GS_HIP(hipMemcpyAsync(dc, h->contrib.count, cn * 4, hipMemcpyDeviceToHost, st));
             GS_HIP(hipMemcpyAsync(dm, h->contrib.max, cn * 4, hipMemcpyDeviceToHost, st));
         }
+        if (idc) {
+            const size_t sb = id_px * (size_t)idc->slots * 4;
+            GS_HIP(hipMemcpyAsync(idc->ids, h->ids.ids, sb, hipMemcpyDeviceToHost, st));
+            if (idc->q) GS_HIP(hipMemcpyAsync(idc->q, h->ids.q, sb, hipMemcpyDeviceToHost, st));
+            if (idc->count) GS_HIP(hipMemcpyAsync(idc->count, h->ids.count, id_px * 4, hipMemcpyDeviceToHost, st));
+        }
         GS_HIP(hipStreamSynchronize(st));
         if (con && cn && con->accumulate) {
             for (size_t i = 0; i < cn; ++i) {
@@ -1949,6 +2017,23 @@ gs_status gs_render_contrib(gs_handle* h, const float* view, const float* proj, 
         return fail(GS_ERR_INVALID_ARG, "gs_render_contrib: null output array");
     const ContribCall cc{mask, out_sum, out_count, out_max, accumulate != 0};
     return render_frame(h, view, proj, W, H, out_rgba, is_device, false, stream, false, nullptr, nullptr, &cc);
+}
+
+static_assert(GS_MAX_ID_SLOTS == gs::kMaxIdSlots && GS_ID_NONE == gs::kIdNone, "ids frames: slot limit and empty id");
+
+gs_status gs_render_ids(gs_handle* h, const float* view, const float* proj, int32_t W, int32_t H, int32_t slots,
+                        float* out_rgba, uint32_t* out_ids, uint32_t* out_q, uint32_t* out_count, int32_t is_device,
+                        void* stream) {
+    // (the arguments are judged first, also on a handle that was never initialised)
+    if (!h) return fail(GS_ERR_INVALID_ARG, "gs_render_ids: null handle");
+    if (!view || !proj || !out_rgba || !out_ids || W <= 0 || H <= 0 || W > 65535 || H > 65535)
+        return fail(GS_ERR_INVALID_ARG, "gs_render_ids: bad arguments");
+    if (slots < 1 || slots > GS_MAX_ID_SLOTS)
+        return fail(GS_ERR_INVALID_ARG, "gs_render_ids: slots must be 1.." + std::to_string(GS_MAX_ID_SLOTS) +
+                                            ", got " + std::to_string(slots));
+    if (is_device < 0 || is_device > 1) return fail(GS_ERR_INVALID_ARG, "gs_render_ids: is_device must be 0 or 1");
+    const IdCall ic{out_ids, out_q, out_count, slots};
+    return render_frame(h, view, proj, W, H, out_rgba, is_device, false, stream, false, nullptr, nullptr, nullptr, &ic);
 }
 
 gs_status gs_render_bgra8(gs_handle* h, const float* view, const float* proj, int32_t W, int32_t H,

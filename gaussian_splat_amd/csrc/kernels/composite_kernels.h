@@ -12,7 +12,8 @@
 // §2.11), composite_feat_kernel and composite_strip_feat_kernel
 // (composite_features.hip, gs_render_features, §2.12), composite_contrib_kernel
 // and composite_strip_contrib_kernel (composite_contrib.hip, gs_render_contrib,
-// §2.13).
+// §2.13), composite_ids_kernel and composite_strip_ids_kernel (composite_ids.hip,
+// gs_render_ids, §2.14).
 //
 // Everything that differs between them is stated in a policy V, what a
 // frame kind composites per pixel beside T:
@@ -36,6 +37,11 @@
 //                 composite_contrib.hip): no pixel is stored; scale, weight and
 //                 scatter turn each fragment's blend weight into its splat's
 //                 totals
+//   kTopK, Top    (IdValues<K>, gs_render_ids, §2.14; composite_ids_kernel and
+//                 composite_strip_ids_kernel, composite_ids.hip) a contrib-shaped
+//                 pass that keeps, per pixel, the K fragments of largest quantised
+//                 weight in registers (Top; insert in scatter's place) and stores
+//                 them at the end of the pixel; 0 and an empty Top elsewhere
 #pragma once
 
 #include <hip/hip_ext.h>
@@ -53,6 +59,8 @@ struct ColourValues {
     struct Own {};
     static constexpr bool kFourth = false, kWholeFrame = false, kContrib = false;
     static constexpr int kWaves = 8;
+    static constexpr int kTopK = 0;
+    struct Top {};
     __device__ __forceinline__ Own gather(const CompositeArgs&, uint32_t) const { return {}; }
     __device__ __forceinline__ float4 values(const Own&, float r, float g, float b) const {
         return make_float4(r, g, b, 0.0f);
@@ -69,6 +77,8 @@ struct DepthValues {
     using Own = float;
     static constexpr bool kFourth = true, kWholeFrame = false, kContrib = false;
     static constexpr int kWaves = 6;
+    static constexpr int kTopK = 0;
+    struct Top {};
     __device__ __forceinline__ Own gather(const CompositeArgs& a, uint32_t id) const { return a.zf[id]; }
     __device__ __forceinline__ float4 values(const Own& zf, float r, float g, float b) const {
         return make_float4(r, g, b, zf);
@@ -95,6 +105,8 @@ struct FeatureValues {
     using Own = float4;
     static constexpr bool kFourth = true, kWholeFrame = true, kContrib = false;
     static constexpr int kWaves = 6;
+    static constexpr int kTopK = 0;
+    struct Top {};
     FeatureArgs f;
     // channels of this launch that exist (1..4; 4 with VIN / VOUT)
     __device__ __forceinline__ uint32_t nch() const {
@@ -149,6 +161,8 @@ struct ContribValues {
     using Own = uint32_t;
     static constexpr bool kFourth = false, kWholeFrame = true, kContrib = true;
     static constexpr int kWaves = 8;
+    static constexpr int kTopK = 0;
+    struct Top {};
     ContribArgs k;
     __device__ __forceinline__ Own gather(const CompositeArgs&, uint32_t id) const { return id; }
     __device__ __forceinline__ float4 values(const Own& id, float, float, float) const {
@@ -176,6 +190,99 @@ struct ContribValues {
             (void)atomicAdd(k.count + id, cnt);
             (void)atomicMax(k.max + id, m);
         }
+    }
+};
+
+// Ids frames (gs_render_ids): each pixel's K fragments of
+// largest quantised weight.  ContribValues' sibling: T per pixel, no colour,
+// the record's id staged where a colour frame stages r, the same q(w) at the
+// same hooks, no mask.  Instead of scattering, a lane keeps per pixel
+//   key[k] = q << 32 | ~id,  k < K, descending (0: an empty slot),
+// and the number of fragments with q > 0.  One unsigned 64-bit order is the
+// call's: q descending, then id ascending; a splat is in a bin's list once, so
+// no two candidates of a pixel compare equal.  A candidate that does not beat
+// key[K - 1] is dropped after that one comparison; one that does replaces it
+// and is moved up by K - 1 compare-exchanges, in the lanes that have one (exec
+// mask); the chain is skipped when no lane of the wave has one (a ballot).
+// store() writes the pixel's slots with vector stores: ~key (GS_ID_NONE for an
+// empty slot), key >> 32 and the count; 16-B stores of ids / q where the call
+// has 4 slots and the array is 16-B aligned (IdArgs::vec), else a dword each.
+template <int K>
+struct IdValues {
+    static_assert(K == 1 || K == 2 || K == 4, "ids composites: 1, 2 or 4 slots in registers");
+    using Own = uint32_t;
+    static constexpr bool kFourth = false, kWholeFrame = true, kContrib = true;
+    static constexpr int kTopK = K;
+    struct Top {
+        unsigned long long key[K];
+        uint32_t n;
+    };
+    IdArgs i;
+    __device__ __forceinline__ Own gather(const CompositeArgs&, uint32_t id) const { return id; }
+    __device__ __forceinline__ float4 values(const Own& id, float, float, float) const {
+        return make_float4(__uint_as_float(id), 0.0f, 0.0f, 0.0f);
+    }
+    __device__ __forceinline__ float scale(bool inside, size_t) const { return inside ? 16777216.0f : 0.0f; }
+    __device__ __forceinline__ uint32_t weight(float w, float scale) const {
+        return (uint32_t)(fminf(fmaxf(w, 0.0f), 1.0f) * scale);
+    }
+    static __device__ __forceinline__ unsigned long long cand(float id_bits, uint32_t q) {
+        return (unsigned long long)q << 32 | (unsigned long long)(~__float_as_uint(id_bits));
+    }
+    static __device__ __forceinline__ void push(Top& t, unsigned long long c, bool beats) {
+        if (beats) {
+            t.key[K - 1] = c;
+#pragma unroll
+            for (int k = K - 1; k > 0; --k) {
+                const unsigned long long lo = t.key[k], hi = t.key[k - 1];
+                t.key[k - 1] = lo > hi ? lo : hi;
+                t.key[k] = lo > hi ? hi : lo;
+            }
+        }
+    }
+    // one record at one pixel (every lane; q = 0 where the update was skipped)
+    __device__ __forceinline__ void insert(Top& t, float id_bits, uint32_t q) const {
+        const unsigned long long c = cand(id_bits, q);
+        const bool beats = q != 0u && c > t.key[K - 1];
+        t.n += q != 0u ? 1u : 0u;
+        if (__ballot(beats) != 0) push(t, c, beats);  // (wave-uniform)
+    }
+    // one record at the strip body's two pixels: one ballot for both chains
+    __device__ __forceinline__ void insert2(Top& ta, Top& tb, float id_bits, uint32_t qa, uint32_t qb) const {
+        const unsigned long long ca = cand(id_bits, qa), cb = cand(id_bits, qb);
+        const bool ba = qa != 0u && ca > ta.key[K - 1], bb = qb != 0u && cb > tb.key[K - 1];
+        ta.n += qa != 0u ? 1u : 0u;
+        tb.n += qb != 0u ? 1u : 0u;
+        if (__ballot(ba || bb) != 0) {  // (wave-uniform)
+            push(ta, ca, ba);
+            push(tb, cb, bb);
+        }
+    }
+    // a finished pixel inside the frame (an empty Top: GS_ID_NONE, 0, 0)
+    __device__ __forceinline__ void store(const Top& t, size_t pix) const {
+        const uint32_t s = (uint32_t)i.slots;  // (<= K; 3 on the K = 4 instance)
+        uint32_t* const pi = i.ids + pix * (size_t)s;
+        if (K == 4 && (i.vec & 1)) {
+            *reinterpret_cast<uint4*>(pi) = make_uint4(~(uint32_t)t.key[0], ~(uint32_t)t.key[1 % K],
+                                                       ~(uint32_t)t.key[2 % K], ~(uint32_t)t.key[3 % K]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+                if ((uint32_t)k < s) pi[k] = ~(uint32_t)t.key[k];
+        }
+        if (i.q) {  // (wave-uniform)
+            uint32_t* const pq = i.q + pix * (size_t)s;
+            if (K == 4 && (i.vec & 2)) {
+                *reinterpret_cast<uint4*>(pq) =
+                    make_uint4((uint32_t)(t.key[0] >> 32), (uint32_t)(t.key[1 % K] >> 32),
+                               (uint32_t)(t.key[2 % K] >> 32), (uint32_t)(t.key[3 % K] >> 32));
+            } else {
+#pragma unroll
+                for (int k = 0; k < K; ++k)
+                    if ((uint32_t)k < s) pq[k] = (uint32_t)(t.key[k] >> 32);
+            }
+        }
+        if (i.count) i.count[pix] = t.n;
     }
 };
 
@@ -373,6 +480,7 @@ __device__ __forceinline__ void composite_tile_body(const CompositeArgs a, uint3
     const size_t pix = (size_t)py * width + px;
     float qscale = 0.0f;  // (V::kContrib) the pixel's weight scale, 0 where the mask leaves it out
     if constexpr (V::kContrib) qscale = v.scale(inside, pix);
+    typename V::Top top{};  // (V::kTopK) the pixel's K heaviest fragments and its fragment count
     // PASS 2: this quadrant was left open by the front list (else its pixels
     // start finished, and were written already)
     const bool resumed = PASS == 2 && (wave == 0 ? oq.x : wave == 1 ? oq.y : wave == 2 ? oq.z : oq.w) != 0u;
@@ -456,7 +564,8 @@ __device__ __forceinline__ void composite_tile_body(const CompositeArgs a, uint3
                 }
             }
             // (every lane again: the record's id is the first staged value)
-            if constexpr (V::kContrib) v.scatter(bb.w, q, q, (uint32_t)__popcll(__ballot(q != 0u)));
+            if constexpr (V::kTopK > 0) v.insert(top, bb.w, q);
+            else if constexpr (V::kContrib) v.scatter(bb.w, q, q, (uint32_t)__popcll(__ballot(q != 0u)));
         }
     };
     // a record's c words: (g, b), the id where the body needs it, and the
@@ -659,6 +768,9 @@ __device__ __forceinline__ void composite_tile_body(const CompositeArgs a, uint3
                 a.out[(size_t)orow * width + px] = o;
         }
     }
+    if constexpr (V::kTopK > 0) {  // (an ids pass: every pixel of the frame, those of empty bins too)
+        if (inside) v.store(top, pix);
+    }
     // the quadrant's record words, after its pixels (a store queued before
     // them would hold the pixel stores' wait, vmcnt counting stores too): its
     // cut position (the end of the last batch it walked with an open pixel,
@@ -773,6 +885,7 @@ __device__ __forceinline__ void composite_strip_body(const CompositeArgs a, uint
         qsA = v.scale(inA, pixA);
         qsB = v.scale(inB, pixB);
     }
+    typename V::Top topA{}, topB{};  // (V::kTopK) per pixel: its K heaviest fragments and its fragment count
     if constexpr (PASS == 2) {
         TA = 0.0f;
         TB = 0.0f;
@@ -853,8 +966,11 @@ __device__ __forceinline__ void composite_strip_body(const CompositeArgs a, uint
             if (sel & 1u) qA = pixel_w(lxA, tu, tv, aa, bb, TA, qsA);
             if (sel & 2u) qB = pixel_w(lxB, tu, tv, aa, bb, TB, qsB);
             // (every lane again: the record's id is the first staged value)
-            v.scatter(bb.y, qA + qB, qA > qB ? qA : qB,
-                      (uint32_t)__popcll(__ballot(qA != 0u)) + (uint32_t)__popcll(__ballot(qB != 0u)));
+            if constexpr (V::kTopK > 0)
+                v.insert2(topA, topB, bb.y, qA, qB);
+            else
+                v.scatter(bb.y, qA + qB, qA > qB ? qA : qB,
+                          (uint32_t)__popcll(__ballot(qA != 0u)) + (uint32_t)__popcll(__ballot(qB != 0u)));
         } else {
             if (sel & 1u) pixel(lxA, tu, tv, aa, bb, dd, TA, A);
             if (sel & 2u) pixel(lxB, tu, tv, aa, bb, dd, TB, B);
@@ -1081,6 +1197,11 @@ __device__ __forceinline__ void composite_strip_body(const CompositeArgs a, uint
     if constexpr (!V::kContrib) {  // (a contrib pass writes no pixel)
         store(resA, keepA, qx, A[0], A[1], A[2], TA, A[kAcc - 1]);  // (C3: the fourth accumulator where one exists)
         store(resB, keepB, qx + 8, B[0], B[1], B[2], TB, B[kAcc - 1]);
+    }
+    if constexpr (V::kTopK > 0) {  // (an ids pass: every pixel of the frame, those of empty bins too)
+        const size_t pix = (size_t)qy * width + qx;
+        if (qx < width && qy < height) v.store(topA, pix);
+        if (qx + 8 < width && qy < height) v.store(topB, pix + 8);
     }
     if constexpr (PASS == 1) {
         if (lane == 0) {

@@ -368,6 +368,24 @@ struct ContribArgs {
 // arrays are combined into, never cleared: the caller zeroes them first for a
 // frame's own totals.
 hipError_t launch_composite_contrib(const CompositeArgs& a, const ContribArgs& k, int mode, hipStream_t st);
+// Ids frames (gs_render_ids; composite_ids.hip): the second
+// parameter of the ids composites, beside CompositeArgs.
+constexpr int kMaxIdSlots = 4;
+constexpr uint32_t kIdNone = 0xFFFFFFFFu;
+struct IdArgs {
+    uint32_t* ids;    // [height][width][slots] splat ids by (q descending, id ascending); kIdNone: empty
+    uint32_t* q;      // [height][width][slots] their quantised weights, 0: empty (null: not wanted)
+    uint32_t* count;  // [height][width] the pixel's fragments with q > 0 (null: not wanted)
+    int slots;        // 1 .. kMaxIdSlots
+    int vec;          // set by the launch: bit 0 ids, bit 1 q take one 16-B store per pixel
+};
+// One pass over the whole lists a (as launch_composite_contrib: pass 0, every
+// row, tile / live50 rules, no cap, no slabs) the frame's colour composite has
+// just read, on its stream: T per pixel, no colour; per pixel the `slots`
+// fragments of largest q(w) (ties: smaller id first) and the number with
+// q > 0.  Every element of ids, q and count is written, for the pixels of
+// empty bins too: every bin of the frame has its workgroups in this launch.
+hipError_t launch_composite_ids(const CompositeArgs& a, const IdArgs& i, int mode, hipStream_t st);
 // One 256-lane workgroup per owned 16x16 tile.  mode 0 = tile rule (A >= 0.99
 // break), 1 = live50 rule (T < 0.01 break), 2 = MLAB k-buffer (a.vals
 // index-ordered, a.dkey set, no cap); with a.cap > 0 only fragments with

@@ -278,6 +278,41 @@ gs_status gs_render_contrib(gs_handle *h, const float view[16], const float proj
                             int32_t height, const uint8_t *mask, float *out_rgba, uint64_t *out_sum,
                             uint32_t *out_count, uint32_t *out_max, int32_t accumulate, int32_t is_device,
                             void *hip_stream);
+/* Colour frame as gs_render, plus which splats make up each pixel: the
+ * question between gs_render_features (what a pixel looks like) and
+ * gs_render_contrib (what a splat puts into the frame).  The candidates of
+ * pixel p are the fragments this frame composites at p with q > 0, q being
+ * gs_render_contrib's quantised weight q(w(i,p)) (same formula, same fp32
+ * operands, same truncation; no mask).  A splat occurs at most once per pixel.
+ * They are ordered by q descending, then by splat index ascending: the tie
+ * rule is on the index, not on the composite's order, so the result does not
+ * depend on how the lists are built or walked.  With p = y*width + x:
+ *   out_ids[p*slots + k] = splat index of the k-th candidate (into the loaded
+ *                          post-crop scene, gs_get_scene's order)
+ *   out_q[p*slots + k]   = its q
+ *   out_count[p]         = the number of candidates (may exceed slots)
+ * Empty slots hold GS_ID_NONE and q = 0.  Every element of every non-NULL
+ * output is written for every pixel of the frame, also where nothing lands:
+ * the caller never clears anything.
+ * 1 <= slots <= GS_MAX_ID_SLOTS, else GS_ERR_INVALID_ARG.  out_q and out_count
+ * may each be NULL (not wanted); out_ids and out_rgba may not.  is_device
+ * covers all four buffers (1: HBM pointers, async on `hip_stream`, the buffers
+ * must not overlap; 0: host pointers, the call syncs); outside {0, 1}:
+ * GS_ERR_INVALID_ARG.  4-B alignment is enough; 16-B aligned out_ids / out_q
+ * with slots == 4 take one 16-B store per pixel.  out_rgba is bit-identical to
+ * gs_render's, and the five render calls may alternate freely on one handle.
+ * An ids frame builds whole bin lists whatever gs_options.depth_split says
+ * (gs_stats.cut_frame == 0), as feature and contrib frames do (DESIGN.md
+ * §2.14).
+ * Tile and live50 modes with cap == 0 on a single-GPU handle; cap > 0, MLAB
+ * mode or a sharded handle: GS_ERR_UNSUPPORTED, nothing is enqueued and
+ * nothing is written.
+ * (Added without an ABI version change: an addition.) */
+#define GS_MAX_ID_SLOTS 4
+#define GS_ID_NONE 0xFFFFFFFFu
+gs_status gs_render_ids(gs_handle *h, const float view[16], const float proj[16], int32_t width, int32_t height,
+                        int32_t slots, float *out_rgba, uint32_t *out_ids, uint32_t *out_q, uint32_t *out_count,
+                        int32_t is_device, void *hip_stream);
 gs_status gs_last_stats(gs_handle *h, gs_stats *out);
 /* stage_timing 2: preprocess and composite kernel times (ms, from the events
  * in their dispatch packets) of the last min(max_frames, 64) frames rendered

@@ -64,6 +64,15 @@ public:
                        uint32_t* count, uint32_t* max, bool accumulate, const simd_float4x4& viewMatrix,
                        const simd_float4x4& projectionMatrix, float viewportWidth, float viewportHeight);
 
+    // Addition (not in the reference): render() plus each pixel's `slots`
+    // (1..GS_MAX_ID_SLOTS) splats of largest quantised blend weight
+    // (gs_render_ids): ids and q are width*height*slots uint32 images in HBM,
+    // slots innermost (GS_ID_NONE / 0 in empty slots), count the width*height
+    // image of the pixel's fragments with q > 0; q and count may be null.
+    void renderIds(void* commandBuffer, void* drawableTexture, int slots, uint32_t* ids, uint32_t* q, uint32_t* count,
+                   const simd_float4x4& viewMatrix, const simd_float4x4& projectionMatrix, float viewportWidth,
+                   float viewportHeight);
+
     // Additions (not in the reference): status of the last call, frame stats.
     gs_status lastStatus() const { return status_; }
     gs_stats lastStats() const;
