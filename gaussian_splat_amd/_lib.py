@@ -74,6 +74,8 @@ SIGNATURES = {
     "gs_render_contrib": (C.c_int, [_P, _FP, _FP, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     "gs_render_ids": (C.c_int, [_P, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
     "gs_render_bgra8": (C.c_int, [_P, _FP, _FP, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    "gs_select": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
+    "gs_prune": (C.c_int, [_P, _P, C.c_int32, _P, _I64P, _P]),
     "gs_last_stats": (C.c_int, [_P, C.POINTER(GsStats)]),
     "gs_kernel_times": (C.c_int, [_P, C.c_int32, _FP, _FP, C.POINTER(C.c_int32)]),
     "gs_project_host": (C.c_int, [_P, _FP, _FP, C.c_int32, C.c_int32, _P, _P, _P]),

@@ -641,6 +641,120 @@ class InstancedSplatRenderer:
                                                                          "sh_rest"))), "gs_get_scene")
         return Scene(**a)
 
+    def select(self, index):
+        """Re-index the scene in place (gs_select): splat j of the new scene is
+        splat index[j] of the old one.  Repeats are allowed and len(index) may
+        exceed the old count; a permutation is the ordinary case; an empty
+        index leaves an empty scene.  `index` is a 1-D CUDA tensor on the
+        handle's device, torch.int32 (uint32 bit patterns, as render_ids returns
+        them: ids[..., 0][mask] feeds straight in) or torch.int64 (range-checked
+        and narrowed): the planes are gathered on the device; or a 1-D numpy
+        integer array: the host path, which also works before initialize().
+        The call waits for the frames in flight.  Afterwards every call sees the
+        new scene, frames equal a fresh renderer's on scene().subset(index) bit
+        for bit, and per-splat arguments and results are in the new order.  A
+        rejected argument (an entry >= getPointCount()) leaves the scene as it
+        was."""
+        kind, a = self._splat_list(index, "index")
+        if kind == "device":
+            import torch
+
+            stream = torch.cuda.current_stream(a.device).cuda_stream
+            check(lib().gs_select(self._h, C.c_void_p(a.data_ptr() if a.numel() else None), int(a.numel()), 1,
+                                  C.c_void_p(stream)), "gs_select")
+        else:
+            check(lib().gs_select(self._h, C.c_void_p(a.ctypes.data if a.size else None), int(a.size), 0, None),
+                  "gs_select")
+
+    def prune(self, keep):
+        """Keep the splats with keep[i] != 0, in their order (gs_prune); returns
+        the new -> old index map, whose length is the new count.  `keep` has
+        getPointCount() entries: a 1-D CUDA tensor on the handle's device,
+        torch.bool or torch.uint8 (the compaction and the gather run on the
+        device; the map comes back as a torch.int32 CUDA tensor holding uint32
+        bits), or a numpy bool / uint8 array (the host path, which also works
+        before initialize(); the map is a numpy uint32 array).  The same as
+        select(flatnonzero(keep))."""
+        n = self.getPointCount()
+        cnt = C.c_int64(0)
+        try:
+            import torch
+        except ImportError:  # (numpy masks need no torch)
+            torch = None
+        if torch is not None and isinstance(keep, torch.Tensor):
+            if keep.dtype not in (torch.bool, torch.uint8):
+                raise ValueError(f"keep must be torch.bool or torch.uint8, got {keep.dtype}")
+            dev = torch.device(f"cuda:{self.device or 0}")
+            if not keep.is_cuda or keep.device != dev:
+                raise ValueError(f"keep must be on the handle's device {dev}, got {keep.device}")
+            if keep.dim() != 1 or keep.numel() != n:
+                raise ValueError(f"keep must have {n} entries in one dimension, got shape {tuple(keep.shape)}")
+            if not keep.is_contiguous():
+                raise ValueError("keep must be contiguous")
+            k8 = keep.view(torch.uint8) if keep.dtype == torch.bool else keep
+            if n == 0:  # (an empty tensor has no address to give)
+                k8 = torch.zeros(1, dtype=torch.uint8, device=dev)
+            out = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            check(lib().gs_prune(self._h, C.c_void_p(k8.data_ptr()), 1, C.c_void_p(out.data_ptr()), C.byref(cnt),
+                                 C.c_void_p(stream)), "gs_prune")
+            return out[:cnt.value]
+        if not isinstance(keep, np.ndarray):
+            raise ValueError("keep must be a torch CUDA tensor or a numpy array")
+        if keep.dtype not in (np.dtype(np.bool_), np.dtype(np.uint8)):
+            raise ValueError(f"keep must be bool or uint8, got {keep.dtype}")
+        if keep.ndim != 1 or keep.size != n:
+            raise ValueError(f"keep must have {n} entries in one dimension, got shape {keep.shape}")
+        if not keep.flags.c_contiguous:
+            raise ValueError("keep must be contiguous")
+        k8 = keep.view(np.uint8) if n else np.zeros(1, np.uint8)
+        out = np.empty(max(n, 1), np.uint32)
+        check(lib().gs_prune(self._h, C.c_void_p(k8.ctypes.data), 0, C.c_void_p(out.ctypes.data), C.byref(cnt), None),
+              "gs_prune")
+        return out[:cnt.value].copy()
+
+    def _splat_list(self, index, name):
+        """An index list argument as ("device", int32 CUDA tensor) or ("host",
+        uint32 numpy array); ValueError for anything else."""
+        try:
+            import torch
+        except ImportError:  # (numpy lists need no torch)
+            torch = None
+        if torch is not None and isinstance(index, torch.Tensor):
+            if index.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"{name} must be torch.int32 or torch.int64, got {index.dtype}")
+            dev = torch.device(f"cuda:{self.device or 0}")
+            if not index.is_cuda or index.device != dev:
+                raise ValueError(f"{name} must be on the handle's device {dev}, got {index.device}")
+            if index.dim() != 1:
+                raise ValueError(f"{name} must have one dimension, got shape {tuple(index.shape)}")
+            if not index.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            if index.numel() > 0xFFFFFFFE:
+                raise ValueError(f"{name} holds more than 2**32 - 2 entries")
+            if index.dtype == torch.int64:
+                if index.numel() and (int(index.min()) < 0 or int(index.max()) > 0xFFFFFFFF):
+                    raise ValueError(f"{name} entries must be 0 .. 2**32 - 1")
+                index = index.to(torch.int32)  # (keeps the low 32 bits: the uint32 pattern)
+            return "device", index
+        if not isinstance(index, np.ndarray):
+            raise ValueError(f"{name} must be a torch CUDA tensor or a numpy integer array")
+        if index.dtype.kind not in "iu":
+            raise ValueError(f"{name} must be an integer array, got {index.dtype}")
+        if index.ndim != 1:
+            raise ValueError(f"{name} must have one dimension, got shape {index.shape}")
+        if not index.flags.c_contiguous:
+            raise ValueError(f"{name} must be contiguous")
+        if index.size > 0xFFFFFFFE:
+            raise ValueError(f"{name} holds more than 2**32 - 2 entries")
+        if index.dtype == np.int32:  # (uint32 bit patterns, as render_ids_host's ids viewed as int32)
+            return "host", index.view(np.uint32)
+        if index.dtype != np.uint32:
+            if index.size and (int(index.min()) < 0 or int(index.max()) > 0xFFFFFFFF):
+                raise ValueError(f"{name} entries must be 0 .. 2**32 - 1")
+            index = index.astype(np.uint32)
+        return "host", index
+
     def subset(self, begin: int, end: int) -> "InstancedSplatRenderer":
         """A renderer over splats [begin, end) of this one's scene (gs_create_subset)."""
         r = InstancedSplatRenderer.__new__(InstancedSplatRenderer)

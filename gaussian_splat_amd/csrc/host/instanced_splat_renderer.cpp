@@ -80,6 +80,16 @@ void InstancedSplatRenderer::renderIds(void* commandBuffer, void* drawableTextur
                             commandBuffer);
 }
 
+bool InstancedSplatRenderer::select(const uint32_t* index, int64_t m) {
+    status_ = gs_select(handle_, index, m, 1, nullptr);
+    return status_ == GS_OK;
+}
+
+bool InstancedSplatRenderer::prune(const uint8_t* keep, uint32_t* outIndex, int64_t* outCount) {
+    status_ = gs_prune(handle_, keep, 1, outIndex, outCount, nullptr);
+    return status_ == GS_OK;
+}
+
 int InstancedSplatRenderer::getPointCount() const { return (int)gs_point_count(handle_); }
 
 gs_stats InstancedSplatRenderer::lastStats() const {

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -2039,6 +2040,229 @@ gs_status gs_render_ids(gs_handle* h, const float* view, const float* proj, int3
 gs_status gs_render_bgra8(gs_handle* h, const float* view, const float* proj, int32_t W, int32_t H,
                           uint8_t* out_bgra, int32_t out_is_device, void* stream) {
     return render_frame(h, view, proj, W, H, out_bgra, out_is_device, true, stream);
+}
+
+// ---- the scene after load: gs_select / gs_prune ---------------
+// What the handle learnt from frames of the old scene: the depth-cut tables
+// and their bin orders, the dilation radii and their controller, the binning
+// model's history (and with it the pair capacity a frame asks for ahead of its
+// scan), the front-only / fused state of the frame being prepared.  Dropped as
+// setup_cuts drops the cuts at a new frame size: a stale cut would still give
+// the exact image (a tile that saturates deeper finishes from its fallback
+// lists), but the next frames would pay for cuts and an order learnt on
+// another scene.  The stats of the last rendered frame stay.
+static void forget_scene_history(gs_handle* h) {
+    for (int s = 0; s < 2; ++s) {
+        h->cut_valid[s] = false;
+        h->cut_r[s] = h->cut_calm[s] = h->dil_r[s] = 0;
+        h->dil_slot[s] = 0;
+        h->dil_wslot[s] = 1;
+    }
+    if (h->host_total) h->host_total[6] = h->host_total[7] = ~0ull;  // (open-quadrant counts of the old scene's frames)
+    h->order = gs_handle::OrderModel{};
+    h->fused_prep = gs_handle::ListPrep{};
+    h->order_pick = -1;
+    h->ppart_words = 0;  // (another block count: the next bin-first frame clears its rows)
+}
+
+// First entry of index[0 .. m) that is >= n, or -1.
+static int64_t first_bad_entry(const uint32_t* index, int64_t m, int64_t n) {
+    for (int64_t j = 0; j < m; ++j)
+        if ((int64_t)index[j] >= n) return j;
+    return -1;
+}
+
+static gs_status bad_entry(const char* who, int64_t j, uint32_t v, int64_t n) {
+    return fail(GS_ERR_INVALID_ARG, std::string(who) + ": index[" + std::to_string(j) + "] = " + std::to_string(v) +
+                                        " is not below the point count " + std::to_string(n));
+}
+
+// A handle that was never initialised: the host planes alone (validated list).
+static gs_status select_host_planes(gs_handle* h, const uint32_t* index, int64_t m, const char* who) {
+    try {
+        gsio::planes_select(h->hp, index, m, &h->hp);  // (built aside: planes shared with other handles stay)
+    } catch (const std::bad_alloc&) {
+        return fail(GS_ERR_OOM, std::string(who) + ": host scene planes");
+    }
+    h->n = m;
+    forget_scene_history(h);
+    return GS_OK;
+}
+
+// An initialised handle, the device idle: gathers the planes of dev_index
+// (m entries on the device) into fresh buffers, builds the same host planes
+// from host_index (the same list on the host) beside the gather, and swaps
+// both in.  A list that is not `trusted` (a caller's device list) is judged by
+// the gather's flag; its host copy is looked through meanwhile only to know
+// whether the host planes can be started before that verdict is in.
+// Nothing of the handle changes on any failure.  Transient peak, HBM and
+// host: the old planes plus the new ones.
+// GS_SELECT_TIMING=1 (debugging aid) prints the call's phases to stderr.
+static gs_status select_planes(gs_handle* h, const uint32_t* dev_index, const uint32_t* host_index, bool trusted,
+                               int64_t m, hipStream_t st, const char* who) {
+    const size_t c = (size_t)std::max<int64_t>(m, 1);
+    const gsio::HostPlanes& hp = h->hp;
+    const bool sh = h->opt.sh_degree > 0;
+    static const bool timing = std::getenv("GS_SELECT_TIMING") != nullptr;
+    using clk = std::chrono::steady_clock;
+    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const clk::time_point t0 = clk::now();
+    DevBuf q0, q1, q2, q3, qsh4, qsh1, flag;
+    GS_HIP(q0.reserve(c * 16));
+    GS_HIP(q1.reserve(c * 16));
+    GS_HIP(q2.reserve(c * 16));
+    GS_HIP(q3.reserve(c * 8));
+    if (sh) {
+        GS_HIP(qsh4.reserve((size_t)std::max(hp.np4(), 1) * c * 16));
+        GS_HIP(qsh1.reserve(c * 4));
+    }
+    GS_HIP(flag.reserve(4));
+    hipEvent_t e0 = nullptr, e1 = nullptr;  // (timing: the gather alone, device time)
+    if (timing && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) e0 = e1 = nullptr;
+    GS_HIP(hipMemsetAsync(flag.ptr, 0, 4, st));
+    if (e0) (void)hipEventRecord(e0, st);
+    const gs::ScenePlanes dst{q0.as<float4>(), q1.as<float4>(), q2.as<float4>(), q3.as<float2>(),
+                              qsh4.as<float4>(), qsh1.as<float>(), (uint32_t)m};
+    GS_HIP(gs::launch_select_gather(h->scene_dev(), h->opt.sh_degree, dev_index, dst, flag.as<uint32_t>(), st));
+    if (e1) (void)hipEventRecord(e1, st);
+    uint32_t bad = 0;
+    GS_HIP(hipMemcpyAsync(&bad, flag.ptr, 4, hipMemcpyDeviceToHost, st));
+    gsio::HostPlanes np;
+    const clk::time_point t1 = clk::now();
+    clk::time_point t2 = t1, t3 = t1;
+    const bool host_ok = trusted || first_bad_entry(host_index, m, h->n) < 0;
+    try {
+        if (host_ok) gsio::planes_select(hp, host_index, m, &np);  // (beside the gather)
+        t2 = clk::now();
+        GS_HIP(hipStreamSynchronize(st));
+        t3 = clk::now();
+        if (bad || !host_ok)
+            return fail(GS_ERR_INVALID_ARG, std::string(who) + ": an index entry is not below the point count " +
+                                                std::to_string(h->n));
+    } catch (const std::bad_alloc&) {
+        (void)hipStreamSynchronize(st);  // (the gather reads buffers this frame of the stack owns)
+        return fail(GS_ERR_OOM, std::string(who) + ": host scene planes");
+    }
+    h->p0 = std::move(q0);
+    h->p1 = std::move(q1);
+    h->p2 = std::move(q2);
+    h->p3 = std::move(q3);
+    if (sh) {
+        h->sh4 = std::move(qsh4);
+        h->sh1 = std::move(qsh1);
+    }
+    h->hp = std::move(np);
+    h->n = m;
+    forget_scene_history(h);
+    if (timing) {
+        float gather_ms = 0.0f;
+        if (e0 && e1) (void)hipEventElapsedTime(&gather_ms, e0, e1);
+        std::fprintf(stderr, "[gsplat] %s: %lld splats: allocate + launch %.3f ms, host planes %.3f ms, "
+                             "wait for the gather %.3f ms (the gather itself %.3f ms), swap + free %.3f ms\n",
+                     who, (long long)m, ms(t0, t1), ms(t1, t2), ms(t2, t3), gather_ms, ms(t3, clk::now()));
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return GS_OK;
+}
+
+gs_status gs_select(gs_handle* h, const uint32_t* index, int64_t m, int32_t is_device, void* stream) {
+    // (the arguments are judged first, also on a handle that was never initialised)
+    if (!h) return fail(GS_ERR_INVALID_ARG, "gs_select: null handle");
+    if (m < 0 || m > (int64_t)UINT32_MAX - 1)
+        return fail(GS_ERR_INVALID_ARG, "gs_select: m must be 0 .. 2^32 - 2, got " + std::to_string(m));
+    if (is_device < 0 || is_device > 1) return fail(GS_ERR_INVALID_ARG, "gs_select: is_device must be 0 or 1");
+    if (!index && m > 0) return fail(GS_ERR_INVALID_ARG, "gs_select: null index");
+    if (h->world != 1) return fail(GS_ERR_UNSUPPORTED, "gs_select: single-GPU handles only");
+    if (h->index_base + m >= (int64_t)UINT32_MAX) return fail(GS_ERR_UNSUPPORTED, "gs_select: index_base + m exceeds 2^32 - 2");
+    if (!is_device) {  // a host list: checked before anything is touched
+        const int64_t j = first_bad_entry(index, m, h->n);
+        if (j >= 0) return bad_entry("gs_select", j, index[j], h->n);
+    }
+    if (!h->initialized) {
+        if (is_device) return fail(GS_ERR_STATE, "gs_select: a device list needs gs_initialize first");
+        return select_host_planes(h, index, m, "gs_select");
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GS_HIP(hipSetDevice(h->device));
+    GS_HIP(hipDeviceSynchronize());  // every frame in flight, on whichever stream; and what `stream` holds
+    if (is_device) {
+        std::vector<uint32_t> down;
+        try {
+            down.resize((size_t)m);
+        } catch (const std::bad_alloc&) {
+            return fail(GS_ERR_OOM, "gs_select: host copy of the index list");
+        }
+        if (m) GS_HIP(hipMemcpy(down.data(), index, (size_t)m * 4, hipMemcpyDeviceToHost));
+        // (the host copy is used only once the gather's flag has cleared the list)
+        return select_planes(h, index, down.data(), false, m, st, "gs_select");
+    }
+    DevBuf up;
+    GS_HIP(up.reserve((size_t)std::max<int64_t>(m, 1) * 4));
+    if (m) GS_HIP(hipMemcpyAsync(up.ptr, index, (size_t)m * 4, hipMemcpyHostToDevice, st));
+    return select_planes(h, up.as<uint32_t>(), index, true, m, st, "gs_select");
+}
+
+gs_status gs_prune(gs_handle* h, const uint8_t* keep, int32_t is_device, uint32_t* out_index, int64_t* out_count,
+                   void* stream) {
+    // (the arguments are judged first, also on a handle that was never initialised)
+    if (!h) return fail(GS_ERR_INVALID_ARG, "gs_prune: null handle");
+    if (!keep) return fail(GS_ERR_INVALID_ARG, "gs_prune: null keep");
+    if (is_device < 0 || is_device > 1) return fail(GS_ERR_INVALID_ARG, "gs_prune: is_device must be 0 or 1");
+    if (h->world != 1) return fail(GS_ERR_UNSUPPORTED, "gs_prune: single-GPU handles only");
+    const int64_t n = h->n;
+    std::vector<uint32_t> list;  // the new -> old map on the host
+    if (!h->initialized) {
+        if (is_device) return fail(GS_ERR_STATE, "gs_prune: a device mask needs gs_initialize first");
+        try {
+            for (int64_t i = 0; i < n; ++i)
+                if (keep[i]) list.push_back((uint32_t)i);
+        } catch (const std::bad_alloc&) {
+            return fail(GS_ERR_OOM, "gs_prune: index list");
+        }
+        const gs_status s = select_host_planes(h, list.data(), (int64_t)list.size(), "gs_prune");
+        if (s != GS_OK) return s;
+        if (out_index && !list.empty()) std::memcpy(out_index, list.data(), list.size() * 4);
+        if (out_count) *out_count = (int64_t)list.size();
+        return GS_OK;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GS_HIP(hipSetDevice(h->device));
+    GS_HIP(hipDeviceSynchronize());  // every frame in flight, on whichever stream; and what `stream` holds
+    const uint32_t nb = gs::select_blocks((uint32_t)n);
+    DevBuf up, dlist, offs;
+    const uint8_t* dkeep = keep;
+    if (!is_device) {
+        GS_HIP(up.reserve((size_t)std::max<int64_t>(n, 1)));
+        if (n) GS_HIP(hipMemcpyAsync(up.ptr, keep, (size_t)n, hipMemcpyHostToDevice, st));
+        dkeep = up.as<uint8_t>();
+    }
+    GS_HIP(dlist.reserve((size_t)std::max<int64_t>(n, 1) * 4));
+    GS_HIP(offs.reserve(((size_t)nb + 1) * 4));
+    GS_HIP(gs::launch_select_compact(dkeep, (uint32_t)n, offs.as<uint32_t>(), dlist.as<uint32_t>(), st));
+    uint32_t count = 0;
+    GS_HIP(hipMemcpyAsync(&count, offs.as<uint32_t>() + nb, 4, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipStreamSynchronize(st));
+    if ((int64_t)count > n) return fail(GS_ERR_DEVICE, "gs_prune: the compaction counted more splats than the mask holds");
+    try {
+        list.resize(count);
+    } catch (const std::bad_alloc&) {
+        return fail(GS_ERR_OOM, "gs_prune: index list");
+    }
+    if (count) GS_HIP(hipMemcpy(list.data(), dlist.ptr, (size_t)count * 4, hipMemcpyDeviceToHost));
+    // (the list the compaction produced, on both sides: every entry is a position of the mask)
+    const gs_status s = select_planes(h, dlist.as<uint32_t>(), list.data(), true, (int64_t)count, st, "gs_prune");
+    if (s != GS_OK) return s;
+    if (out_index && count) {
+        if (is_device) {
+            GS_HIP(hipMemcpyAsync(out_index, dlist.ptr, (size_t)count * 4, hipMemcpyDeviceToDevice, st));
+            GS_HIP(hipStreamSynchronize(st));  // (dlist goes with this call)
+        } else {
+            std::memcpy(out_index, list.data(), (size_t)count * 4);
+        }
+    }
+    if (out_count) *out_count = (int64_t)count;
+    return GS_OK;
 }
 
 gs_status gs_last_stats(gs_handle* h, gs_stats* out) {

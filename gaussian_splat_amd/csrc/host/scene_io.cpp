@@ -267,4 +267,25 @@ void planes_subset(const HostPlanes& src, int64_t b, int64_t e, HostPlanes* out)
     if (src.tail()) std::memcpy(out->sh1.data(), src.sh1.data() + b, (size_t)m * 4);
 }
 
+void planes_select(const HostPlanes& src, const uint32_t* index, int64_t m, HostPlanes* out) {
+    HostPlanes dst;  // (src may be *out: built aside, then put in place)
+    dst.alloc(m, src.sh_degree);
+    const int np4 = src.np4();
+    const bool tail = src.tail();
+    const size_t n = (size_t)src.n, mm = (size_t)std::max<int64_t>(m, 0);
+    parallel_chunks(m, chunks_for(m), [&](int, int64_t b, int64_t e) {
+        for (int64_t j = b; j < e; ++j) {
+            const size_t i = index[j];
+            std::memcpy(dst.p0.data() + 4 * j, src.p0.data() + 4 * i, 16);
+            std::memcpy(dst.p1.data() + 4 * j, src.p1.data() + 4 * i, 16);
+            std::memcpy(dst.p2.data() + 4 * j, src.p2.data() + 4 * i, 16);
+            std::memcpy(dst.p3.data() + 2 * j, src.p3.data() + 2 * i, 8);
+            for (int k = 0; k < np4; ++k)
+                std::memcpy(dst.sh4.data() + ((size_t)k * mm + (size_t)j) * 4, src.sh4.data() + ((size_t)k * n + i) * 4, 16);
+            if (tail) std::memcpy(dst.sh1.data() + j, src.sh1.data() + i, 4);
+        }
+    });
+    *out = std::move(dst);
+}
+
 }  // namespace gsio

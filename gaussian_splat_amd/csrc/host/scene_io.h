@@ -61,5 +61,9 @@ gs_status planes_from_ply(const char* path, float crop_radius, bool crop, int sh
                           bool* handled);
 // Splats [b, e) of src (the whole range shares src's buffers).
 void planes_subset(const HostPlanes& src, int64_t b, int64_t e, HostPlanes* out);
+// Splat j of out = splat index[j] of src, j < m (every entry < src.n; repeats
+// allowed), into new buffers: src's are shared and stay as they are.  out may
+// be src.  Throws std::bad_alloc.
+void planes_select(const HostPlanes& src, const uint32_t* index, int64_t m, HostPlanes* out);
 
 }  // namespace gsio

@@ -485,4 +485,26 @@ hipError_t launch_shard_pack(const float4* rec, const uint32_t* rlo, const uint3
                              const uint32_t* dest_total, uint32_t nblocks, float4* send, hipStream_t st);
 // dst[i] += src[i] for n4 float4s.
 hipError_t launch_accumulate(float4* dst, const float4* src, size_t n4, hipStream_t st);
+
+// ---- select.hip (gs_select / gs_prune: the scene re-indexed on the device) --
+constexpr uint32_t kSelectBlock = 1024;  // mask bytes per compaction block
+inline uint32_t select_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + kSelectBlock - 1) / kSelectBlock); }
+// Stable compaction of a keep mask (n bytes, nonzero = keep): index[0 .. c) =
+// the kept positions, ascending; offsets (select_blocks(n) + 1 words of
+// scratch) ends with the blocks' exclusive offsets and offsets[nb] = c.
+// index holds n words; entries from c on are not written.
+hipError_t launch_select_compact(const uint8_t* keep, uint32_t n, uint32_t* offsets, uint32_t* index, hipStream_t st);
+// The planes a gather writes (SceneDev's layout over n splats).
+struct ScenePlanes {
+    float4 *p0, *p1, *p2;
+    float2* p3;
+    float4* sh4;
+    float* sh1;
+    uint32_t n;
+};
+// dst splat j = src splat index[j], j < dst.n, every plane of sh_degree.  An
+// entry >= src.n is not dereferenced: *flag (zeroed by the caller) becomes
+// nonzero and that splat of dst is left unwritten.
+hipError_t launch_select_gather(const SceneDev& src, int sh_degree, const uint32_t* index, const ScenePlanes& dst,
+                                uint32_t* flag, hipStream_t st);
 }  // namespace gs

@@ -313,6 +313,46 @@ gs_status gs_render_contrib(gs_handle *h, const float view[16], const float proj
 gs_status gs_render_ids(gs_handle *h, const float view[16], const float proj[16], int32_t width, int32_t height,
                         int32_t slots, float *out_rgba, uint32_t *out_ids, uint32_t *out_q, uint32_t *out_count,
                         int32_t is_device, void *hip_stream);
+/* The scene after load: re-index the handle's own scene, on the device where
+ * it lives.
+ * gs_select: the handle's scene becomes: splat j of the new scene = splat
+ * index[j] of the old one, j = 0 .. m-1.  0 <= m <= 2^32 - 2; every entry must
+ * be < gs_point_count(h); repeats are allowed (a splat may occur twice and m
+ * may exceed the old count), a permutation is the ordinary case.  index may be
+ * NULL only when m == 0: the scene is then empty.
+ * gs_prune: stable compaction: the new scene is the old scene's splats with
+ * keep[i] != 0, in ascending i (keep: gs_point_count(h) bytes); the same as
+ * gs_select with that ascending list.  out_index (optional, of keep's memory
+ * kind, capacity: the old count) receives the new -> old map in its first
+ * *out_count entries, the rest is not written; out_count (optional, always a
+ * host pointer) the new count.
+ * is_device covers index, or keep and out_index (1: HBM pointers, read after
+ * the work already queued on `hip_stream`; 0: host pointers); outside {0, 1}:
+ * GS_ERR_INVALID_ARG.  Both calls are synchronous for the host: they wait for
+ * every frame the handle has in flight, on whichever stream (they synchronise
+ * the device), and return with the new scene in place.  Not a per-frame call.
+ * Afterwards gs_point_count, gs_get_scene, gs_create_subset and the groups
+ * created from the handle see the new scene, and every render call gives the
+ * frame a fresh handle created from the selected scene with the same options
+ * gives, bit for bit; per-splat arguments and results (feature rows, contrib
+ * arrays, ids) are in the new order.  What the handle learnt from earlier
+ * frames (depth cuts, bin orders, the binning model) is dropped.
+ * gs_last_stats and gs_sorted_pairs_host keep describing the last rendered
+ * frame, in that frame's indices, until the next one.
+ * On failure the handle is unchanged: an entry >= the count, m out of range,
+ * a NULL handle / index / keep: GS_ERR_INVALID_ARG (a host list is checked
+ * before anything is touched, a device list by the gather itself, which forms
+ * no address from a bad entry); GS_ERR_OOM: the new planes are built beside
+ * the old ones and swapped in on success, so the transient peak, host and
+ * HBM, is the old planes plus the new ones; a handle configured with
+ * gs_shard_configure(world > 1): GS_ERR_UNSUPPORTED.
+ * A handle that was never initialised takes host lists (its host planes are
+ * re-indexed and a later gs_initialize uploads the selected scene);
+ * is_device == 1 on it: GS_ERR_STATE.
+ * (Added without an ABI version change: an addition.) */
+gs_status gs_select(gs_handle *h, const uint32_t *index, int64_t m, int32_t is_device, void *hip_stream);
+gs_status gs_prune(gs_handle *h, const uint8_t *keep, int32_t is_device, uint32_t *out_index, int64_t *out_count,
+                   void *hip_stream);
 gs_status gs_last_stats(gs_handle *h, gs_stats *out);
 /* stage_timing 2: preprocess and composite kernel times (ms, from the events
  * in their dispatch packets) of the last min(max_frames, 64) frames rendered

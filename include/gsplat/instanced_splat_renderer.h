@@ -73,6 +73,17 @@ public:
                    const simd_float4x4& viewMatrix, const simd_float4x4& projectionMatrix, float viewportWidth,
                    float viewportHeight);
 
+    // Additions (not in the reference): the scene re-indexed on the device
+    // (gs_select, gs_prune).  select: splat j of the new scene = splat index[j]
+    // of the old one, index an m-entry uint32 list in HBM.  prune: the splats
+    // with keep[i] != 0 stay, in order (keep: getPointCount() bytes in HBM);
+    // outIndex (may be null; HBM, getPointCount() entries) receives the new ->
+    // old map, *outCount (may be null; host) the new count.  Both wait for the
+    // frames in flight and return true with the new scene in place; on false
+    // the scene is unchanged and lastStatus() says why.
+    bool select(const uint32_t* index, int64_t m);
+    bool prune(const uint8_t* keep, uint32_t* outIndex, int64_t* outCount);
+
     // Additions (not in the reference): status of the last call, frame stats.
     gs_status lastStatus() const { return status_; }
     gs_stats lastStats() const;
